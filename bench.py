@@ -14,12 +14,19 @@ RCCL broadcast before the timed region; no data-path collective per step (SURVEY
 rank renders K frames.  Without a launcher (`WORLD_SIZE` unset) `--gpus N` starts the N ranks itself, before
 anything in this process has touched a GPU.  Rank 0 prints one JSON line.
 
-The line carries two timed legs of the same workload: `value` / `roofline` for the default binning
-(tile_rect = 1: a Gaussian is binned into the bounding box of its alpha >= 1/255 region) and `upstream_rect`
-for the reference's own binning (tile_rect = 0: the 3-sigma square, whose tile lists, ranges and num_rendered
-are upstream's bit for bit).  At N = 1 it also holds `roofline.traffic` (HBM bytes of the dominant kernel) and
-`roofline.valu` (issued VALU instructions) from rocprofv3 --pmc passes over a few frames of the same workload,
-run as child processes of this command before it touches the GPU itself (--no-pmc skips them).
+A plain run measures the headline figure only: set-up, warm-up, the K timed steps of the default binning
+(tile_rect = 1: a Gaussian is binned into the bounding box of its alpha >= 1/255 region), the line.
+
+--full adds everything else, as a second timed leg and untimed passes around the first: per-stage times and
+`roofline` of the default binning, `upstream_rect` for the reference's own binning (tile_rect = 0: the 3-sigma
+square, whose tile lists, ranges and num_rendered are upstream's bit for bit) and, at N = 1, the CPU baseline,
+`roofline.traffic` (HBM bytes of the dominant kernel) and `roofline.valu` (issued VALU instructions) from
+rocprofv3 --pmc passes over a few frames of the same workload, run as child processes of this command before it
+touches the GPU itself (--no-upstream-leg, --no-cpu-baseline, --no-pmc skip those parts).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32): the
+image(s), radii, loss, gradients and, with --train-step, the updated state.  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import csv
@@ -87,6 +94,28 @@ def stage_flops(pairs):
     return {"render_fwd": float(pairs) * 26, "render_bwd": float(pairs) * 71}
 
 
+DUMP_BYTES = 60 * 10**6  # array data --dump-outputs writes at most: under 64 MB with the .npy headers
+
+
+def write_outputs(arrays, out_dir):
+    """Writes every array of {name: float32 ndarray} as out_dir/<name>.npy.  Arrays are written whole while they fit
+    DUMP_BYTES together; past it, every array above a common element count is replaced by a fixed, seeded random sample
+    of that many of its elements (flattened, in index order) and the smaller ones stay whole -- the same elements in
+    every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = sorted(a.size for a in arrays.values())
+    left, cap = DUMP_BYTES // 4, None
+    for i, n in enumerate(sizes):
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    for name, a in arrays.items():
+        if cap is not None and a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -116,10 +145,15 @@ def parse_args(argv=None):
                          "renders frames r, r + N, ...: render.py:51-62; BASELINE config 4 is --workload config4 "
                          "--total-frames 300 --gpus 8); value = total frames / the slowest rank's time.  Default 0: weak "
                          "scaling, every rank renders --steps frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-stage times, roofline and VALU figures, "
+                         "the rocprofv3 --pmc child passes, the upstream-binning leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, %d MB at most)" % (DUMP_BYTES // 10**6))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-upstream-leg", action="store_true", help="skip the second timed leg (tile_rect = 0)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (traffic / valu become null)")
+    ap.add_argument("--no-upstream-leg", action="store_true", help="--full: skip the second timed leg (tile_rect = 0)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc child passes (traffic / valu become null)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the run rocprofv3 wraps: frames only
     return ap.parse_args(argv)
 
@@ -262,7 +296,7 @@ def main(argv=None):
     affinity = pin_rank_to_cores(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))) if world > 1 else None
 
     pmc, pmc_note = {}, "skipped (--no-pmc)"
-    if world == 1 and not args.pmc_child and not args.no_pmc:
+    if args.full and world == 1 and not args.pmc_child and not args.no_pmc:
         pmc, pmc_note = pmc_passes(args, argv)  # children; this process has not initialised the GPU yet
 
     rehearsal = False
@@ -362,6 +396,8 @@ def main(argv=None):
         stats = DensifyStats(N, dev)
 
     def step(i):
+        """One frame of the hot path; returns (render package, loss -- None without a backward)."""
+        loss = None
         for f in GaussianCloud.FIELDS:
             getattr(cloud, f).grad = None
         if args.prepass:
@@ -382,7 +418,28 @@ def main(argv=None):
         else:
             with torch.no_grad():
                 pkg = render(cams[i], cloud, pipe, bg)
-        return pkg
+        return pkg, loss
+
+    def train_state():
+        """Every tensor --train-step updates: the parameters, Adam's state, the densification statistics."""
+        ts = [getattr(cloud, f) for f in GaussianCloud.FIELDS] + [stats.max_radii2D, stats.xyz_gradient_accum, stats.denom]
+        for st in opt.state.values():
+            ts += [st["step"], st["exp_avg"], st["exp_avg_sq"]]
+        return ts
+
+    def outputs_of(pkg, loss):
+        """What the caller of a step receives from it, as float32 host arrays."""
+        out = {"render": pkg.render, "radii": pkg.radii, "opacity_render": pkg.opacity_render, "loss": loss}
+        if loss is not None:
+            out["grad_means2D"] = pkg.viewspace_points.grad
+            for f in GaussianCloud.FIELDS:
+                out["grad_" + f] = getattr(cloud, f).grad
+            if args.prepass:
+                out["grad_rotation_precomp"] = cloud.rotation_precomp.grad
+        if opt is not None:  # the state after the update
+            out.update({f: getattr(cloud, f) for f in GaussianCloud.FIELDS})
+            out.update(max_radii2D=stats.max_radii2D, xyz_gradient_accum=stats.xyz_gradient_accum, denom=stats.denom)
+        return {k: v.detach().float().cpu().numpy() for k, v in out.items() if v is not None}
 
     if args.pmc_child:  # under rocprofv3 --pmc: a few frames, nothing timed, nothing printed
         for i in range(4):
@@ -396,39 +453,46 @@ def main(argv=None):
               "gaussian_bwd": ["gaussian_bwd"]}
     kernel_stages = ["preprocess", "render_fwd", "render_bwd", "gaussian_bwd"]
 
-    def run_leg(tile_rect):
-        """One complete measurement in one binning mode: per-stage HIP events on 5 untimed frames, W warm-up steps,
-        then EXACTLY K timed steps between barrier + synchronize on both sides, max over ranks."""
+    def run_leg(tile_rect, full, keep_outputs):
+        """One complete measurement in one binning mode: W warm-up steps, then EXACTLY K timed steps between barrier +
+        synchronize on both sides, max over ranks.  full: also per-stage HIP events on 5 untimed frames, the dominant
+        kernel bracketed in the timed loop, per-stage passes behind it.  keep_outputs: the host copy of what the last
+        timed step returned goes into the result as `outputs`."""
         dgr._TILE_RECT = tile_rect
         dgr.release_shared_geometry()
         for i in range(3):
             step(i)
         torch.cuda.synchronize()
-        _lib.profile_enable(True)
-        for i in range(3, 8):
-            pkg = step(i)
-        stages = _lib.profile_collect()
-        _lib.profile_enable(False)
-        stage_ms = {k: v[0] / 5.0 for k, v in stages.items()}  # ms per frame (5 profiled frames)
-        dominant = max(kernel_stages, key=lambda k: stage_ms.get(k, 0.0))
-        # D and n_contrib of the benchmark frame (reported with every number: cost is a function of D)
-        with torch.no_grad():
-            vis = int((pkg.radii > 0).sum().item())
-        D, mean_contrib, quad_hits, pairs_valid = frame_stats(cams[0], cloud, pipe, bg)
+        if full:
+            _lib.profile_enable(True)
+            for i in range(3, 8):
+                pkg, _ = step(i)
+            stages = _lib.profile_collect()
+            _lib.profile_enable(False)
+            stage_ms = {k: v[0] / 5.0 for k, v in stages.items()}  # ms per frame (5 profiled frames)
+            dominant = max(kernel_stages, key=lambda k: stage_ms.get(k, 0.0))
+            # D and n_contrib of the benchmark frame (reported with every number: cost is a function of D)
+            with torch.no_grad():
+                vis = int((pkg.radii > 0).sum().item())
+            D, mean_contrib, quad_hits, pairs_valid = frame_stats(cams[0], cloud, pipe, bg)
         # untimed: ~0.7 s of back-to-back steps right before the warm-up, so that the chip's clocks have settled under
         # THIS load (the statistics above leave the GPU idle for a while; a timed region that starts on an idle chip
         # reads 10-25 % slow for its first hundreds of steps), then the W warm-up steps and the K timed ones
-        # The timed loop brackets the dominant kernel with two HIP events per step.  Creating an event and recording it
-        # for the first time cost ~0.1-0.2 ms each (seen as a timed loop whose first steps take 3-4 ms): the stage timer
-        # therefore already runs during the settle and warm-up steps below, so that every event the timed loop takes from
-        # the pool has been created AND recorded on this stream before.
-        _lib.profile_reserve(2 * K + 64)
-        _lib.profile_enable(True, stage=dominant)
+        if full:
+            # The timed loop brackets the dominant kernel with two HIP events per step.  Creating an event and recording
+            # it for the first time cost ~0.1-0.2 ms each (seen as a timed loop whose first steps take 3-4 ms): the stage
+            # timer therefore already runs during the settle and warm-up steps below, so that every event the timed loop
+            # takes from the pool has been created AND recorded on this stream before.
+            _lib.profile_reserve(2 * K + 64)
+            _lib.profile_enable(True, stage=dominant)
         # A full collection of the interpreter's cyclic garbage collector walks every object torch has created at import
         # (60-100 ms, observed as ONE step of the timed loop taking that long): collect now -- BEFORE the settle steps,
         # nothing may leave the GPU idle between them and the timed loop -- and keep it off until the timing is done.
         gc.collect()
         gc.disable()
+        # --train-step: the settle below runs for a fixed TIME, i.e. a varying number of updates; the state it leaves is
+        # put back afterwards, so that the warm-up and the timed steps start from the same state in every run
+        saved = [t.detach().clone() for t in train_state()] if opt is not None else None
         # ... over the frames the warm-up and the timed loop will render (at least once each): the pair count differs from
         # frame to frame, and a binning capacity or scratch size the caching allocator has not seen yet is a hipMalloc of
         # milliseconds -- inside a timed region of 20 steps one of those is 20 % of the reading
@@ -439,10 +503,16 @@ def main(argv=None):
                 step(i % nf)
                 i += 1
             torch.cuda.synchronize()
+        if saved is not None:
+            with torch.no_grad():
+                for t, s in zip(train_state(), saved):
+                    t.copy_(s)
+            del saved
         for i in range(Wm):
             step(8 + i)
         torch.cuda.synchronize()
-        _lib.profile_collect()  # returns every event used so far to the pool: the timed loop takes them from there
+        if full:
+            _lib.profile_collect()  # returns every event used so far to the pool: the timed loop takes them from there
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -452,7 +522,9 @@ def main(argv=None):
         for i in range(K):
             if trace:
                 h0 = time.perf_counter()
-            step(8 + Wm + i)
+            last = step(8 + Wm + i)
+            if i < K - 1:
+                last = None  # (a step's outputs hold its autograd state: alive during the next step, they would add to its memory)
             if trace:
                 h1 = time.perf_counter() - h0
                 if h1 > worst[0]:
@@ -470,37 +542,44 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         gc.enable()
-        # the shader clock the chip holds under a VALU-bound load, measured NOW, right behind the timed loop (an FMA stream
-        # of ~1 ms on every SIMD: s_memtime against the constant 100 MHz counter) -- for roofline.binding
-        clock_hz = _lib.clock_probe(dev) if world == 1 else None
-        dom = _lib.profile_collect().get(dominant, (0.0, 0))
-        _lib.profile_enable(False)
-        # Per-stage times, taken NOW: right behind the timed loop, on the same settled clocks and over the same frames, one
-        # stage per pass (two HIP events per call -- bracketing every stage at once adds ~2-4 us of event handling per
-        # stage to the frame).  Taken before the settle steps, as until round 2, they read ~15 % high and added up to more
-        # than ms_per_step.
-        post = {}
-        for name in sorted(stage_ms):
-            _lib.profile_enable(True, stage=name)
-            for i in range(8):
-                step(8 + Wm + (i % max(K, 1)))
-            got = _lib.profile_collect().get(name)
-            if got and got[1]:
-                post[name] = got[0] / 8.0  # ms per frame (a stage may run more than once per frame)
-        _lib.profile_enable(False)
-        stage_ms = post or stage_ms
+        if full:
+            # the shader clock the chip holds under a VALU-bound load, measured NOW, right behind the timed loop (an FMA
+            # stream of ~1 ms on every SIMD: s_memtime against the constant 100 MHz counter) -- for roofline.binding
+            clock_hz = _lib.clock_probe(dev) if world == 1 else None
+            dom = _lib.profile_collect().get(dominant, (0.0, 0))
+            _lib.profile_enable(False)
+        outputs = outputs_of(*last) if keep_outputs else None  # (before any further step replaces the gradients)
+        last = None
+        if full:
+            # Per-stage times, taken NOW: right behind the timed loop, on the same settled clocks and over the same frames,
+            # one stage per pass (two HIP events per call -- bracketing every stage at once adds ~2-4 us of event handling
+            # per stage to the frame).  Taken before the settle steps, as until round 2, they read ~15 % high and added up
+            # to more than ms_per_step.
+            post = {}
+            for name in sorted(stage_ms):
+                _lib.profile_enable(True, stage=name)
+                for i in range(8):
+                    step(8 + Wm + (i % max(K, 1)))
+                got = _lib.profile_collect().get(name)
+                if got and got[1]:
+                    post[name] = got[0] / 8.0  # ms per frame (a stage may run more than once per frame)
+            _lib.profile_enable(False)
+            stage_ms = post or stage_ms
         if use_dist:
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        total_frames = args.total_frames if strong else world * K
+        per_rank = total_frames / world  # frames per rank (strong scaling: the average; the slowest rank sets `elapsed`)
+        ms_step = elapsed / per_rank * 1e3
+        leg = {"fps": total_frames / elapsed, "ms_per_step": ms_step, "elapsed": elapsed, "K": K, "outputs": outputs}
+        if not full:
+            return leg
         px = W * H
         sb = stage_bytes(N, D, px)
         dom_ms = dom[0] / max(dom[1], 1)
         achieved = sb[dominant] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         frame_bytes = sum(sb.values()) if do_bwd else sb["preprocess"] + sb["binning"] + sb["render_fwd"]
-        total_frames = args.total_frames if strong else world * K
-        per_rank = total_frames / world  # frames per rank (strong scaling: the average; the slowest rank sets `elapsed`)
-        ms_step = elapsed / per_rank * 1e3
         grouped = {g: sum(stage_ms.get(st, 0.0) for st in ss) for g, ss in groups.items()}
         in_groups = {st for ss in groups.values() for st in ss}
         for st, v in stage_ms.items():  # stages outside the five SURVEY 8(d) groups: losses, the backward's tile order + mark fill
@@ -514,9 +593,8 @@ def main(argv=None):
         residual = ms_step - sum(grouped.values())
         grouped["outside_stages"] = max(residual, 0.0) if world == 1 else 0.0
         stage_frac = {g: round(sb[g] / (grouped[g] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for g in sb if grouped.get(g, 0.0) > 0}
-        return {
-            "fps": total_frames / elapsed, "ms_per_step": ms_step, "elapsed": elapsed, "D": D, "visible": vis, "K": K,
-            "stages_frac": stage_frac,
+        return dict(leg, **{
+            "D": D, "visible": vis, "stages_frac": stage_frac,
             "mean_contrib": mean_contrib, "quad_hits": quad_hits, "pairs_valid": pairs_valid, "dominant": dominant, "dom_ms": dom_ms, "stage_ms": stage_ms,
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
@@ -525,70 +603,17 @@ def main(argv=None):
                          "frame_frac": round(frame_bytes * (K / elapsed) / 1e9 / HBM_PEAK_GBS, 5)},
             "stages_ms": {g: round(v, 4) for g, v in grouped.items()},
             "outside_stages_signed": round(residual, 4) if world == 1 else None, "stage_pass_frames": 8, "clock_hz": clock_hz,
-        }
+        })
 
     default_rect = int(os.environ.get("GSPLAT_TILE_RECT", "1"))
-    main_leg = run_leg(default_rect)
+    main_leg = run_leg(default_rect, args.full, keep_outputs=(args.dump_outputs is not None and rank == 0))
     up_leg = None
-    if not args.no_upstream_leg and default_rect != 0:
-        up_leg = run_leg(0)
+    if args.full and not args.no_upstream_leg and default_rect != 0:
+        up_leg = run_leg(0, True, keep_outputs=False)
         dgr._TILE_RECT = default_rect
         dgr.release_shared_geometry()
 
     if rank == 0:
-        roof = main_leg["roofline"]
-        dominant = main_leg["dominant"]
-        # ---- measured HBM traffic and VALU issue of the render kernels (rocprofv3 --pmc children of THIS run)
-        per_kernel = {}
-        for kname, stage in KERNEL_STAGE.items():
-            c = pmc.get(kname)
-            if c:
-                per_kernel[kname] = {"stage": stage, "traffic": traffic_bytes(c),
-                                     "valu_insts": int(c["SQ_INSTS_VALU"]) if "SQ_INSTS_VALU" in c else None}
-        dom_kernels = [k for k, st in KERNEL_STAGE.items() if st == dominant and k in per_kernel and per_kernel[k]["traffic"]]
-        if dom_kernels:
-            roof["traffic"] = sum(per_kernel[k]["traffic"]["bytes"] for k in dom_kernels)
-            roof["traffic_over_algorithmic"] = round(roof["traffic"] / max(roof["algorithmic_bytes"], 1), 3)
-        roof["traffic_source"] = pmc_note
-        # (pixel, Gaussian) pairs the render kernels evaluate: 64 pixels per (quadrant, Gaussian) entry up to the quadrant's
-        # last contributor (what the backward iterates; the forward stops a little later, when all 64 pixels are done)
-        pairs_eval = 64.0 * main_leg["quad_hits"]
-        fl = stage_flops(pairs_eval)
-        valu = {}
-        for kname, stage in (("render_fwd_kernel", "render_fwd"), ("render_bwd_kernel", "render_bwd")):
-            ms = main_leg["dom_ms"] if stage == dominant else main_leg["stage_ms"].get(stage, 0.0)
-            if ms <= 0:
-                continue
-            rec = {"kernel_ms": round(ms, 4), "pairs_evaluated": pairs_eval,
-                   # pairs actually composited (alpha >= 1/255 before the pixel is done; gs_pair_stats, outside the timed
-                   # region) and their share of what the kernel evaluates: the head-room finer culling than 8 x 8 could have
-                   "pairs_valid": float(main_leg["pairs_valid"]),
-                   "pairs_valid_over_evaluated": round(main_leg["pairs_valid"] / max(pairs_eval, 1.0), 4),
-                   "flops_8d": fl[stage], "tflops_8d": round(fl[stage] / (ms * 1e-3) / 1e12, 2),
-                   "frac_of_fp32_vector_peak": round(fl[stage] / (ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4)}
-            insts = per_kernel.get(kname, {}).get("valu_insts")
-            if insts:
-                # a wave64 VALU instruction occupies its SIMD-32 for 2 cycles: slots = SIMDs x clock x t / 2
-                rec["insts_per_launch"] = insts
-                rec["issue_slot_util"] = round(insts * 2.0 / (SIMDS * CLOCK_HZ * ms * 1e-3), 4)
-            valu[stage] = rec
-        if dominant in valu and "issue_slot_util" in valu[dominant]:
-            # the ceiling that actually binds the dominant kernel, next to the HBM one the contract asks for
-            roof["binding"] = {"ceiling": "VALU issue slots (one wave64 instruction per SIMD-32 every 2 cycles)",
-                               "frac": valu[dominant]["issue_slot_util"], "kernel": dominant,
-                               # the chip does not hold 2.4 GHz under a VALU-bound load: measured live in this run, right
-                               # behind the timed loop (gs_clock_probe: an FMA stream of ~1 ms on every SIMD, s_memtime
-                               # against s_memrealtime)
-                               "measured_clock_hz": main_leg["clock_hz"],
-                               "clock_source": "gs_clock_probe behind the timed loop of this run",
-                               "frac_at_measured_clock": (round(valu[dominant]["issue_slot_util"] * CLOCK_HZ / main_leg["clock_hz"], 4)
-                                                          if main_leg.get("clock_hz") else None)}
-        roof["valu"] = {"peak_tflops": VALU_PEAK_TFLOPS, "simds": SIMDS, "clock_hz": CLOCK_HZ,
-                        "note": "secondary ceiling (SURVEY.md 8d): the render kernels are VALU-issue bound, not HBM bound; "
-                                "issue_slot_util = SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x kernel time); "
-                                "flops_8d = SURVEY 8(d)'s 26 / 71 flop per (pixel, Gaussian) pair x the pairs the kernels "
-                                "evaluate (64 x quadrant-list entries up to each quadrant's last contributor)",
-                        **valu}
         out = {
             "metric": "render fps (fwd+bwd) @200k Gaussians 1024x1024 SH3" if args.workload == "config3"
             else "render fps (%s) @%s" % ("fwd+bwd" if do_bwd else "fwd", args.workload),
@@ -603,33 +628,93 @@ def main(argv=None):
                 (", covariance + colours precomputed by the fused pre-pass" if args.prepass else "") +
                 (", + densification statistics + Adam step" if args.train_step else "") +
                 ("" if args.opacity == "none" else ", + opacity render (%s) with 0.1 L1 mask loss" % args.opacity)),
-                "tile_rect": default_rect, "l1": (args.l1 if do_bwd else None), "long_lists": dgr._LONG_LISTS, "gaussians": N, "visible": main_leg["visible"], "width": W, "height": H,
-                "sh_degree": deg, "num_rendered": main_leg["D"], "mean_n_contrib": round(main_leg["mean_contrib"], 2),
+                "tile_rect": default_rect, "l1": (args.l1 if do_bwd else None), "long_lists": dgr._LONG_LISTS, "gaussians": N, "width": W, "height": H,
+                "sh_degree": deg,
                 "frames_per_rank": ([args.total_frames // world, (args.total_frames + world - 1) // world] if strong else K),
                 "total_frames": args.total_frames if strong else world * K, "ranks": world,
                 "backend": "none" if not use_dist else ("gloo (REHEARSAL: all ranks on one GPU)" if rehearsal else "nccl (RCCL)"),
                 "rank_cpu_affinity": affinity,
                 "parallelism": "frames sharded x%d" % world + (" (REHEARSAL: all ranks on one GPU, gloo)" if rehearsal else ""),
                 "broadcast_s": round(t_bcast, 6), "state_checksums": state_sums},
-            "roofline": roof,
-            # per frame, measured right behind the timed loop, one stage per pass; the entries add up to ms_per_step
-            # (`outside_stages` = torch glue launches, gaps, host pacing); stages_frac = algorithmic bytes / time / 8 TB/s
-            "stages_ms": main_leg["stages_ms"],
-            "stages_frac": main_leg["stages_frac"],
-            "stages_detail_ms": {k: round(v, 4) for k, v in sorted(main_leg["stage_ms"].items())},
-            # `outside_stages` is derived (ms_per_step - sum of the stage times), clamped at 0 in stages_ms; the signed residual:
-            "outside_stages_derived": {"signed_ms": main_leg["outside_stages_signed"], "stage_pass_frames": main_leg["stage_pass_frames"]},
         }
-        if up_leg is not None:
-            # the reference's own binning (3-sigma squares): tile lists / ranges / num_rendered are upstream's bit for bit
-            out["upstream_rect"] = {"tile_rect": 0, "value": round(up_leg["fps"], 2), "unit": "frames/s",
-                                    "ms_per_step": round(up_leg["ms_per_step"], 4), "num_rendered": up_leg["D"],
-                                    "mean_n_contrib": round(up_leg["mean_contrib"], 2), "roofline": up_leg["roofline"],
-                                    "stages_ms": up_leg["stages_ms"], "stages_frac": up_leg["stages_frac"]}
-        if per_kernel:
-            out["pmc_per_kernel"] = per_kernel
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cloud, W, H, deg, gt, do_bwd, args.cpu_threads)
+        if args.full:
+            out["config"].update(visible=main_leg["visible"], num_rendered=main_leg["D"],
+                                 mean_n_contrib=round(main_leg["mean_contrib"], 2))
+            roof = main_leg["roofline"]
+            dominant = main_leg["dominant"]
+            # ---- measured HBM traffic and VALU issue of the render kernels (rocprofv3 --pmc children of THIS run)
+            per_kernel = {}
+            for kname, stage in KERNEL_STAGE.items():
+                c = pmc.get(kname)
+                if c:
+                    per_kernel[kname] = {"stage": stage, "traffic": traffic_bytes(c),
+                                         "valu_insts": int(c["SQ_INSTS_VALU"]) if "SQ_INSTS_VALU" in c else None}
+            dom_kernels = [k for k, st in KERNEL_STAGE.items() if st == dominant and k in per_kernel and per_kernel[k]["traffic"]]
+            if dom_kernels:
+                roof["traffic"] = sum(per_kernel[k]["traffic"]["bytes"] for k in dom_kernels)
+                roof["traffic_over_algorithmic"] = round(roof["traffic"] / max(roof["algorithmic_bytes"], 1), 3)
+            roof["traffic_source"] = pmc_note
+            # (pixel, Gaussian) pairs the render kernels evaluate: 64 pixels per (quadrant, Gaussian) entry up to the quadrant's
+            # last contributor (what the backward iterates; the forward stops a little later, when all 64 pixels are done)
+            pairs_eval = 64.0 * main_leg["quad_hits"]
+            fl = stage_flops(pairs_eval)
+            valu = {}
+            for kname, stage in (("render_fwd_kernel", "render_fwd"), ("render_bwd_kernel", "render_bwd")):
+                ms = main_leg["dom_ms"] if stage == dominant else main_leg["stage_ms"].get(stage, 0.0)
+                if ms <= 0:
+                    continue
+                rec = {"kernel_ms": round(ms, 4), "pairs_evaluated": pairs_eval,
+                       # pairs actually composited (alpha >= 1/255 before the pixel is done; gs_pair_stats, outside the timed
+                       # region) and their share of what the kernel evaluates: the head-room finer culling than 8 x 8 could have
+                       "pairs_valid": float(main_leg["pairs_valid"]),
+                       "pairs_valid_over_evaluated": round(main_leg["pairs_valid"] / max(pairs_eval, 1.0), 4),
+                       "flops_8d": fl[stage], "tflops_8d": round(fl[stage] / (ms * 1e-3) / 1e12, 2),
+                       "frac_of_fp32_vector_peak": round(fl[stage] / (ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4)}
+                insts = per_kernel.get(kname, {}).get("valu_insts")
+                if insts:
+                    # a wave64 VALU instruction occupies its SIMD-32 for 2 cycles: slots = SIMDs x clock x t / 2
+                    rec["insts_per_launch"] = insts
+                    rec["issue_slot_util"] = round(insts * 2.0 / (SIMDS * CLOCK_HZ * ms * 1e-3), 4)
+                valu[stage] = rec
+            if dominant in valu and "issue_slot_util" in valu[dominant]:
+                # the ceiling that actually binds the dominant kernel, next to the HBM one the contract asks for
+                roof["binding"] = {"ceiling": "VALU issue slots (one wave64 instruction per SIMD-32 every 2 cycles)",
+                                   "frac": valu[dominant]["issue_slot_util"], "kernel": dominant,
+                                   # the chip does not hold 2.4 GHz under a VALU-bound load: measured live in this run, right
+                                   # behind the timed loop (gs_clock_probe: an FMA stream of ~1 ms on every SIMD, s_memtime
+                                   # against s_memrealtime)
+                                   "measured_clock_hz": main_leg["clock_hz"],
+                                   "clock_source": "gs_clock_probe behind the timed loop of this run",
+                                   "frac_at_measured_clock": (round(valu[dominant]["issue_slot_util"] * CLOCK_HZ / main_leg["clock_hz"], 4)
+                                                              if main_leg.get("clock_hz") else None)}
+            roof["valu"] = {"peak_tflops": VALU_PEAK_TFLOPS, "simds": SIMDS, "clock_hz": CLOCK_HZ,
+                            "note": "secondary ceiling (SURVEY.md 8d): the render kernels are VALU-issue bound, not HBM bound; "
+                                    "issue_slot_util = SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x kernel time); "
+                                    "flops_8d = SURVEY 8(d)'s 26 / 71 flop per (pixel, Gaussian) pair x the pairs the kernels "
+                                    "evaluate (64 x quadrant-list entries up to each quadrant's last contributor)",
+                            **valu}
+            out.update({
+                "roofline": roof,
+                # per frame, measured right behind the timed loop, one stage per pass; the entries add up to ms_per_step
+                # (`outside_stages` = torch glue launches, gaps, host pacing); stages_frac = algorithmic bytes / time / 8 TB/s
+                "stages_ms": main_leg["stages_ms"],
+                "stages_frac": main_leg["stages_frac"],
+                "stages_detail_ms": {k: round(v, 4) for k, v in sorted(main_leg["stage_ms"].items())},
+                # `outside_stages` is derived (ms_per_step - sum of the stage times), clamped at 0 in stages_ms; the signed residual:
+                "outside_stages_derived": {"signed_ms": main_leg["outside_stages_signed"], "stage_pass_frames": main_leg["stage_pass_frames"]},
+            })
+            if up_leg is not None:
+                # the reference's own binning (3-sigma squares): tile lists / ranges / num_rendered are upstream's bit for bit
+                out["upstream_rect"] = {"tile_rect": 0, "value": round(up_leg["fps"], 2), "unit": "frames/s",
+                                        "ms_per_step": round(up_leg["ms_per_step"], 4), "num_rendered": up_leg["D"],
+                                        "mean_n_contrib": round(up_leg["mean_contrib"], 2), "roofline": up_leg["roofline"],
+                                        "stages_ms": up_leg["stages_ms"], "stages_frac": up_leg["stages_frac"]}
+            if per_kernel:
+                out["pmc_per_kernel"] = per_kernel
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cloud, W, H, deg, gt, do_bwd, args.cpu_threads)
+        if args.dump_outputs is not None:
+            write_outputs(main_leg["outputs"], args.dump_outputs)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -156,3 +156,26 @@ def test_ranks_get_disjoint_core_slices():
     r = subprocess.run([sys.executable, "-c", code, "0", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300,
                        cwd=root, env=dict(os.environ, GSPLAT_BENCH_NO_AFFINITY="1"))
     assert json.loads(r.stdout.strip().splitlines()[-1]) == [None, sorted(os.sched_getaffinity(0))]
+
+
+def test_dump_outputs_stay_within_64_mb_and_sample_the_same_elements_in_every_run(tmp_path):
+    """bench.write_outputs (--dump-outputs): arrays that fit the budget together are written whole; past it the largest
+    ones are cut to a seeded sample of their elements, in index order, and two writes of the same arrays are identical."""
+    import numpy as np
+
+    import bench
+    arrays = {"big": np.arange(12_000_000, dtype=np.float32), "mid": np.arange(9_000_000, dtype=np.float32),
+              "small": np.arange(1000, dtype=np.float32), "loss": np.float32(0.25).reshape(())}
+    for d in ("a", "b"):
+        bench.write_outputs(arrays, str(tmp_path / d))
+    total = 0
+    for name, full in arrays.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.tobytes() == b.tobytes(), name
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+        if full.size <= 1000:
+            assert np.array_equal(a, full), name
+        else:  # a sample: distinct elements of the array, in index order
+            assert 0 < a.size < full.size and np.all(np.diff(a) > 0) and a[-1] < full.size, name
+    assert total <= 64 * 10**6
+    assert bench.parse_args(["--dump-outputs", "x"]).dump_outputs == "x" and not bench.parse_args([]).full

@@ -70,3 +70,24 @@ def test_one_rank_on_the_rccl_backend_runs_the_whole_multi_rank_code_path():
     cs = d["config"]["state_checksums"]
     assert len(cs) == 1 and cs[0] != 0 and d["config"]["broadcast_s"] > 0 and d["value"] > 0
 
+
+
+def test_plain_run_dumps_the_last_steps_outputs_the_same_in_every_run(tmp_path):
+    """A plain run reports the headline figure only and, with --dump-outputs, writes what its last timed step returned as
+    float32 .npy files.  Two runs with the same arguments write the same bits -- with --train-step too, whose settle phase
+    (a fixed time, so a varying number of updates) must not leak into the state the timed steps start from."""
+    import numpy as np
+    args = ("--gpus", "1", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--train-step")
+    for d in ("a", "b"):
+        line = _bench(*args, "--dump-outputs", str(tmp_path / d))
+        assert line["steps"] == 3 and line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1) < 1e-2
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert not {"roofline", "stages_ms", "upstream_rect", "cpu_baseline"} & set(line)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"render.npy", "radii.npy", "loss.npy", "grad_means2D.npy", "grad_xyz.npy", "grad_shs.npy", "xyz.npy",
+            "denom.npy"} <= set(names)
+    assert np.load(tmp_path / "a" / "render.npy").shape == (3, 256, 256)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.tobytes() == b.tobytes(), n

@@ -59,7 +59,11 @@ def test_camera_matrices_match_reference_graphics_utils():
         assert np.array_equal(cam.world_view_transform.numpy(), g["world_view_%d" % k])
         assert np.array_equal(cam.projection_matrix.numpy(), g["proj_%d" % k])
         assert np.array_equal(cam.full_proj_transform.numpy(), g["full_proj_%d" % k])
-        assert np.array_equal(cam.camera_center.numpy(), g["center_%d" % k])
+        # camera_center = inverse(world_view)[3, :3] in fp32 (the reference's formula, bit for bit on this host); the
+        # fixture's value is that inverse on another host, and LAPACK's fp32 inverse rounds differently from CPU to CPU
+        wv = torch.from_numpy(g["world_view_%d" % k])
+        assert np.array_equal(cam.camera_center.numpy(), wv.inverse()[3, :3].numpy())
+        np.testing.assert_array_max_ulp(cam.camera_center.numpy(), g["center_%d" % k], maxulp=4)
         assert focal2fov(500.0 * W / 512.0, W) == fovx
 
 

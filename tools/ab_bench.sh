@@ -5,7 +5,7 @@ mkdir -p $OUT
 for pass in 1 2; do
   for spec in "$@"; do
     label=${spec%%|*}; rest=${spec#*|}; envs=${rest%%|*}; args=${rest#*|}
-    env $envs python bench.py --no-pmc --no-cpu-baseline $args > $OUT/${label}_$pass.json 2> $OUT/${label}_$pass.err
+    env $envs python bench.py --full --no-pmc --no-cpu-baseline $args > $OUT/${label}_$pass.json 2> $OUT/${label}_$pass.err
     python - "$OUT/${label}_$pass.json" "$label" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats --output-format csv -- python3 $ROOT/bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-pmc --no-upstream-leg "$@" > $OUT/${TAG}_stats.log 2>&1 || { tail -20 $OUT/${TAG}_stats.log; exit 1; }
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats --output-format csv -- python3 $ROOT/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-pmc --no-upstream-leg "$@" > $OUT/${TAG}_stats.log 2>&1 || { tail -20 $OUT/${TAG}_stats.log; exit 1; }
 cd $ROOT
 cp $(ls $OUT/${TAG}_stats/*/*kernel_stats.csv | head -1) $OUT/${TAG}_kernel_stats.csv
 rm -rf $OUT/${TAG}_stats

@@ -7,9 +7,9 @@
 TAG=$1; WL=${2:-config3}; NAME=${3:-$WL}; shift; shift; shift
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
-python bench.py --steps 200 --warmup 20 --workload $WL "$@" > $OUT/${TAG}_${NAME}_bench.json 2> $OUT/${TAG}_${NAME}_bench.err || exit 1
+python bench.py --full --steps 200 --warmup 20 --workload $WL "$@" > $OUT/${TAG}_${NAME}_bench.json 2> $OUT/${TAG}_${NAME}_bench.err || exit 1
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_${NAME}_stats --output-format csv -- python3 $OLDPWD/bench.py --steps 30 --warmup 3 --workload $WL --no-cpu-baseline --no-pmc "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_${NAME}_stats --output-format csv -- python3 $OLDPWD/bench.py --full --steps 30 --warmup 3 --workload $WL --no-cpu-baseline --no-pmc "$@" > /dev/null 2>&1
 cd $OLDPWD
 cp $(ls $OUT/${TAG}_${NAME}_stats/*/*kernel_stats.csv | head -1) $OUT/${TAG}_${NAME}_kernel_stats.csv
 rm -rf $OUT/${TAG}_${NAME}_stats

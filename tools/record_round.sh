@@ -3,7 +3,7 @@
 # the two-rank rehearsals, the graph-capture log.  Usage: tools/record_round.sh TAG   (files: gpurun_out/<TAG>_*)
 TAG=$1
 OUT=$PWD/gpurun_out
-B="python bench.py --no-cpu-baseline --no-pmc"
+B="python bench.py --full --no-cpu-baseline --no-pmc"
 line() { python - "$1" <<'PY'
 import json, sys
 try:
