@@ -760,6 +760,48 @@ int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, d
     return launch_adam(n_tensors, tensors, beta1, beta2, eps, step, (hipStream_t)stream);
 }
 
+// ---- densification cycle (densify.hip).  N < 2^30: the map packs a source index and a two-bit slot into 32 bits, and
+// N' <= 2 N stays an int32
+#define GS_DENSIFY_MAX_N (1 << 30)
+int gs_densify_workspace_bytes(int32_t N, size_t* out) {
+    if (!out || N < 0 || N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
+    *out = densify_workspace_bytes(N);
+    return GS_OK;
+}
+int gs_densify_plan(const GsDensifyPlan* p, void* workspace, size_t workspace_bytes, int32_t* count_host_pinned,
+                    void* stream) {
+    GS_CAPTURE_OK_IF(stream, count_host_pinned == nullptr);
+    if (!p || !workspace || p->N < 0 || p->N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
+    if (p->N > 0 && !p->prune_mask && (!p->scaling || !p->opacity || !p->grad_accum || !p->denom)) return GS_E_BAD_ARG;
+    if (workspace_bytes < densify_workspace_bytes(p->N)) return GS_E_WORKSPACE;
+    return launch_densify_plan(*p, workspace, count_host_pinned, (hipStream_t)stream);
+}
+int gs_densify_apply(int32_t N, int32_t N_new, const void* workspace, size_t workspace_bytes, int32_t n_tensors,
+                     const GsDensifyTensor* tensors, const float* scaling, const float* rotation, const float* noise,
+                     void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || N >= GS_DENSIFY_MAX_N || N_new < 0 || N_new > 2 * N || !workspace || n_tensors < 0 ||
+        n_tensors > GS_DENSIFY_MAX_TENSORS || (n_tensors > 0 && !tensors))
+        return GS_E_BAD_ARG;
+    if (workspace_bytes < densify_workspace_bytes(N)) return GS_E_WORKSPACE;
+    for (int k = 0; k < n_tensors; k++) {
+        const GsDensifyTensor& t = tensors[k];
+        if (t.width <= 0 || t.kind < GS_DENSIFY_COPY || t.kind > GS_DENSIFY_CHILD_SCALING) return GS_E_BAD_ARG;
+        if (N_new > 0 && (!t.dst || (t.kind != GS_DENSIFY_ZERO && !t.src))) return GS_E_BAD_ARG;
+        if ((t.kind == GS_DENSIFY_CHILD_POSITION || t.kind == GS_DENSIFY_CHILD_SCALING) && t.width != 3) return GS_E_BAD_ARG;
+        if (t.kind == GS_DENSIFY_CHILD_POSITION && N_new > 0 && (!scaling || !rotation || !noise)) return GS_E_BAD_ARG;
+    }
+    if (N_new == 0 || n_tensors == 0) return GS_OK;
+    return launch_densify_apply(N, N_new, workspace, n_tensors, tensors, scaling, rotation, noise, (hipStream_t)stream);
+}
+int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, float* exp_avg, float* exp_avg_sq,
+                     void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (N > 0 && (!opacity_in || !opacity_out))) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_reset_opacity(N, opacity_in, opacity_out, exp_avg, exp_avg_sq, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

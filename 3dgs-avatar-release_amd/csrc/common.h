@@ -527,6 +527,12 @@ int launch_tile_lists(const uint4* ranklist, const uint32_t* chunk_pairs, uint32
 int launch_densify_stats(int N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
                          float* xyz_gradient_accum, float* denom, hipStream_t s);
 int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s);
+// densification cycle (densify.hip)
+size_t densify_workspace_bytes(int N);
+int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_host, hipStream_t s);
+int launch_densify_apply(int N, int N_new, const void* workspace, int n, const GsDensifyTensor* tensors,
+                         const float* scaling, const float* rotation, const float* noise, hipStream_t s);
+int launch_reset_opacity(int N, const float* in, float* out, float* exp_avg, float* exp_avg_sq, hipStream_t s);
 
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,

@@ -40,7 +40,8 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_last_hip_error", "gs_last_stage", "gs_build_info", "gs_profile_enable", "gs_profile_filter", "gs_profile_collect",
            "gs_l1_loss_workspace_bytes", "gs_l1_loss", "gs_bce_loss", "gs_ssim_workspace_bytes", "gs_ssim_forward", "gs_ssim_backward",
            "gs_build_covariance", "gs_build_covariance_backward", "gs_sh2rgb", "gs_sh2rgb_backward", "knn_points", "gs_densify_stats", "gs_adam_step",
-           "gs_opacity_image", "gs_backward_with_opacity", "gs_tuning", "gs_profile_reserve", "gs_image_bytes_for", "gs_backward_with_second", "gs_clock_probe", "gs_pair_stats", "gs_xcc_probe"]
+           "gs_opacity_image", "gs_backward_with_opacity", "gs_tuning", "gs_profile_reserve", "gs_image_bytes_for", "gs_backward_with_second", "gs_clock_probe", "gs_pair_stats", "gs_xcc_probe",
+           "gs_densify_workspace_bytes", "gs_densify_plan", "gs_densify_apply", "gs_reset_opacity"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -50,6 +51,22 @@ GS_ADAM_MAX_TENSORS = 16
 class GsAdamTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsAdamTensor
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("n", c_int64), ("lr", c_float)]
+
+
+GS_DENSIFY_MAX_TENSORS = 24  # include/gsplat_mi355.h: GS_DENSIFY_*
+GS_DENSIFY_COPY, GS_DENSIFY_ZERO_IF_NEW, GS_DENSIFY_ZERO, GS_DENSIFY_CHILD_POSITION, GS_DENSIFY_CHILD_SCALING = 0, 1, 2, 3, 4
+GS_DENSIFY_F_KEEP, GS_DENSIFY_F_CLONE, GS_DENSIFY_F_SPLIT, GS_DENSIFY_F_PRUNE = 1, 2, 4, 8
+GS_DENSIFY_F_CHILD_PRUNE, GS_DENSIFY_F_CLONE_KEPT, GS_DENSIFY_F_CHILDREN_KEPT = 16, 32, 64
+
+
+class GsDensifyPlan(ctypes.Structure):  # include/gsplat_mi355.h: GsDensifyPlan
+    _fields_ = [("N", c_int32), ("scaling", c_void_p), ("opacity", c_void_p), ("grad_accum", c_void_p), ("denom", c_void_p),
+                ("prune_mask", c_void_p), ("grad_threshold", c_float), ("split_scale", c_float), ("min_opacity", c_float),
+                ("max_world_scale", c_float), ("max_screen_size", c_float), ("prune_size", c_int32)]
+
+
+class GsDensifyTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsDensifyTensor
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("width", c_int32), ("kind", c_int32)]
 
 
 _lock = threading.Lock()
@@ -112,6 +129,11 @@ def load():
         L.knn_points.argtypes = [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_densify_stats.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_adam_step.argtypes = [c_int32, POINTER(GsAdamTensor), c_double, c_double, c_double, c_int64, c_void_p]
+        L.gs_densify_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
+        L.gs_densify_plan.argtypes = [POINTER(GsDensifyPlan), c_void_p, c_size_t, c_void_p, c_void_p]
+        L.gs_densify_apply.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, POINTER(GsDensifyTensor), c_void_p,
+                                       c_void_p, c_void_p, c_void_p]
+        L.gs_reset_opacity.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

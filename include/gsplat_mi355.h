@@ -47,7 +47,7 @@ extern "C" {
  *                          empty: read the count afterwards, outside the graph)
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
- *   gs_densify_stats
+ *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -315,6 +315,63 @@ int gs_densify_stats(int32_t N, const int32_t* radii, const float* viewspace_gra
                      float* xyz_gradient_accum, float* denom, void* stream);
 int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step,
                  void* stream);
+
+/* ---- densification cycle (scene/gaussian_model.py:263-266,311-462; train.py:217-227): clone, split and prune with the
+ * Adam-state surgery, and reset_opacity.  The full semantics are spelled out at the top of csrc/densify.hip.
+ * gs_densify_plan: classifies the N sources (clone / split / prune, or prune by `prune_mask` alone), and builds in
+ *   `workspace` (gs_densify_workspace_bytes(N) bytes) the destination -> source map of the result and its row count N'.
+ *   N' stays on the device; if `count_host_pinned` is non-NULL it is also copied there (HOST-pinned int32, same stream;
+ *   the caller synchronises before reading it).  Workspace byte 0..N-1 = the per-source GS_DENSIFY_F_* flags.
+ * gs_densify_apply: writes every output tensor of the cycle in ONE launch, by destination row: dst [N_new, width] from
+ *   src [N, width] through the plan's map, per the tensor's kind.  `N_new` is the plan's N' (rows past the plan's own
+ *   count are written as zeros).  A GS_DENSIFY_CHILD_POSITION tensor (xyz, width 3) also reads `scaling` [N,3],
+ *   `rotation` [N,4] and `noise` [N,2,3] (standard-normal z of the two children of every source; only split sources'
+ *   rows are read); a GS_DENSIFY_CHILD_SCALING tensor has width 3.  dst must not alias any source.
+ * gs_reset_opacity: opacity_out = logit(min(sigmoid(opacity_in), 0.01)) (in place allowed); exp_avg / exp_avg_sq (each
+ *   NULL or [N]) are zeroed.
+ * N = 0 and N' = 0 are legal (nothing to write).  The library allocates nothing. ---- */
+#define GS_DENSIFY_MAX_TENSORS 24
+#define GS_DENSIFY_COPY 0            /* dst row = src row of its source (a clone or child copies its source's row)        */
+#define GS_DENSIFY_ZERO_IF_NEW 1     /* an Adam moment: surviving originals copy, clones and children start at zero      */
+#define GS_DENSIFY_ZERO 2            /* a statistic: zeros of the new N (src may be NULL)                                 */
+#define GS_DENSIFY_CHILD_POSITION 3  /* xyz: children get R(normalize(q)) (z (.) exp(scaling)) + xyz                      */
+#define GS_DENSIFY_CHILD_SCALING 4   /* scaling: children get log(exp(s) / 1.6)                                           */
+#define GS_DENSIFY_F_KEEP 1          /* flags: the original row survives                                                  */
+#define GS_DENSIFY_F_CLONE 2         /* selected for cloning                                                              */
+#define GS_DENSIFY_F_SPLIT 4         /* selected for splitting                                                            */
+#define GS_DENSIFY_F_PRUNE 8         /* the source's own values are pruned (its row, and its clone's)                     */
+#define GS_DENSIFY_F_CHILD_PRUNE 16  /* its children are pruned                                                           */
+#define GS_DENSIFY_F_CLONE_KEPT 32
+#define GS_DENSIFY_F_CHILDREN_KEPT 64
+typedef struct GsDensifyPlan {
+    int32_t N;
+    const float* scaling;      /* [N,3] log scales */
+    const float* opacity;      /* [N] logits */
+    const float* grad_accum;   /* [N] xyz_gradient_accum (densify mode) */
+    const float* denom;        /* [N] (densify mode) */
+    const uint8_t* prune_mask; /* NULL: densify mode.  Else prune_points(mask): rows with mask != 0 go, nothing is added,
+                                * and scaling / opacity / grad_accum / denom are not read (may be NULL) */
+    float grad_threshold;      /* (float) opt.densify_grad_threshold */
+    float split_scale;         /* (float)(percent_dense * extent), the product taken in double */
+    float min_opacity;         /* (float) opt.opacity_threshold */
+    float max_world_scale;     /* (float)(0.1 * extent) */
+    float max_screen_size;     /* (float) max_screen_size */
+    int32_t prune_size;        /* max_screen_size is set (truthy): the world-size and screen-size prune tests apply */
+} GsDensifyPlan;
+typedef struct GsDensifyTensor {
+    const float* src; /* [N, width] */
+    float* dst;       /* [N_new, width] */
+    int32_t width;    /* floats per row, > 0 */
+    int32_t kind;     /* GS_DENSIFY_* */
+} GsDensifyTensor;
+int gs_densify_workspace_bytes(int32_t N, size_t* out);
+int gs_densify_plan(const GsDensifyPlan* plan, void* workspace, size_t workspace_bytes, int32_t* count_host_pinned,
+                    void* stream);
+int gs_densify_apply(int32_t N, int32_t N_new, const void* workspace, size_t workspace_bytes, int32_t n_tensors,
+                     const GsDensifyTensor* tensors, const float* scaling, const float* rotation, const float* noise,
+                     void* stream);
+int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, float* exp_avg, float* exp_avg_sq,
+                     void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`:
  *  geom:    0 depths f32[P]        1 tiles_touched u32[P]   2 splat records f32[P,12]
