@@ -385,6 +385,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         opacities = _f32c(opacities, "opacities")
         scales = _f32c(scales, "scales")
         rotations = _f32c(rotations, "rotations")
+        if rotations is not None:
+            rotations = _lib.contiguous_aligned(rotations)  # read (and their gradients written) as float4
         cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp")
         dev = means3D.device
         P = int(means3D.shape[0])

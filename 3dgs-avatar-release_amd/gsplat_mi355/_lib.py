@@ -277,3 +277,17 @@ def ptr(t):
     if t is None or t.numel() == 0:
         return None
     return t.data_ptr()
+
+
+def is_aligned(t, nbytes=16):
+    """True when `t.data_ptr()` is a multiple of `nbytes` (an empty tensor counts as aligned: it is passed as NULL).  A
+    contiguous view can start at any element of its storage (`img[1:]` of a (3, H, W) image with H W odd starts 4 bytes
+    past a 16-byte boundary); kernels that read or write a caller's tensor as float4 need 16."""
+    return t.numel() == 0 or t.data_ptr() % nbytes == 0
+
+
+def contiguous_aligned(t, nbytes=16):
+    """`t.contiguous()`, copied once more into fresh (allocator-aligned) storage when that view does not start on an
+    `nbytes` boundary."""
+    t = t.contiguous()
+    return t if is_aligned(t, nbytes) else t.clone()

@@ -47,6 +47,19 @@ class Plan(object):
     def flags(self):
         return self.ws[:self.n]
 
+    @staticmethod
+    def map_offset(n, ws_bytes):
+        """Byte offset of the row map in a workspace of `ws_bytes` for N = n: it is the last region, u32[2 N] padded to
+        256 bytes (csrc/densify.hip dn_carve)."""
+        return ws_bytes - ((2 * n * 4 + 255) & ~255)
+
+    def row_map(self):
+        """The plan's destination -> source map as (src, slot), int64 [n_new] each (slot 0 original, 1 clone, 2 / 3 first /
+        second child): what apply_plan will gather by."""
+        off = self.map_offset(self.n, self.ws.numel())
+        m = self.ws[off:off + 4 * self.n_new].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        return m & 0x3FFFFFFF, m >> 30
+
     def masks(self):
         """The reference's selection masks over the N sources: clone, split, and `keep` (the original row survives)."""
         f = self.flags.to(torch.int32)

@@ -60,6 +60,8 @@ def build_covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):
     matrices (`rotation_precomp`), exactly as utils/general_utils.py:194-207 dispatches on the last dimension."""
     scaling = _dev32(scaling, "scaling")
     rotation = _dev32(rotation, "rotation")
+    if rotation.shape[-1] == 4:
+        rotation = _lib.contiguous_aligned(rotation)  # quaternions are read (and their gradients written) as float4
     if scaling.dim() != 2 or scaling.shape[1] != 3:
         raise ValueError("scaling: (N,3) expected")
     is_matrix = rotation.shape[-1] != 4

@@ -200,7 +200,9 @@ def l1_loss(network_output, gt):
         raise ValueError("l1_loss: empty input")
     if network_output.shape != gt.shape:
         network_output, gt = torch.broadcast_tensors(network_output, gt)
-    return _L1Loss.apply(network_output.contiguous(), gt.contiguous())
+    # the kernel reads both operands as float4: a contiguous view that starts between 16-byte boundaries (img[1:] of a
+    # (3, H, W) image with H W odd) is copied first
+    return _L1Loss.apply(_lib.contiguous_aligned(network_output), _lib.contiguous_aligned(gt))
 
 
 class _Ssim(torch.autograd.Function):

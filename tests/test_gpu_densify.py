@@ -350,3 +350,125 @@ def test_training_across_changes_of_n(monkeypatch):
     assert losses[149] < losses[0], losses[::10]
     assert losses[199] < losses[150], losses[150::10]
     assert len(set(sizes)) >= 2
+
+
+# ---- sweep across block, scan-round and tail edges against the numpy restatement (oracle/densify_ref.py).  A block is
+# 1024 sources, the scan carries its totals across rounds of 256 blocks: N = 262 145 is the first N with a carry, ~1.1 M
+# has five rounds and a partly filled last block.  Compared through the row map and a gather on the device.
+
+SWEEP_N = [1, 1023, 1024, 1025, 4097, 262143, 262144, 262145, 263169, 1100001]
+SWEEP_KW = dict(grad_threshold=0.0002, percent_dense=0.01, extent=1.0, min_opacity=0.05)
+
+
+def _sweep_state(n, kind="fused"):
+    """A synthetic state of N rows (oracle/densify_ref.py: stretches layout where N has the rounds for it) on the device,
+    with FusedAdam state on every group; f_dc, f_rest and the moments are device noise that only travels with the rows."""
+    from oracle import densify_ref as dr
+    host = dr.synthetic_state(dr.layout(n, "stretches" if n > 530 * 1024 else "mixed", seed=n), seed=n)
+    assert dr.check_margins(host, **SWEEP_KW)
+    gen = torch.Generator(device=DEV).manual_seed(n)
+    rnd = lambda *s: torch.randn(s, device=DEV, generator=gen)
+    params = {k: torch.nn.Parameter(torch.from_numpy(host[k]).to(DEV)) for k in ("xyz", "opacity", "scaling", "rotation")}
+    params["f_dc"], params["f_rest"] = torch.nn.Parameter(rnd(n, 1, 3)), torch.nn.Parameter(rnd(n, 15, 3))
+    opt = _optimizer(kind, params)
+    for k in GROUPS:
+        opt.state[params[k]] = {"step": torch.tensor(7.0), "exp_avg": rnd(*params[k].shape),
+                                "exp_avg_sq": rnd(*params[k].shape).abs()}
+    stats = {k: torch.from_numpy(host[k]).to(DEV) for k in STATS}
+    return host, params, opt, stats
+
+
+def _check_rows(new, opt, params, moments, src, slot, new_stats=None, stats=None):
+    """Every copied value bit for bit through the map: parameters (children's xyz / scaling excepted), surviving moments,
+    zeros for new rows' moments; statistics zero (densify) or gathered (prune_points)."""
+    src_d, old_d = torch.from_numpy(src).to(DEV), torch.from_numpy(slot == 0).to(DEV)
+    moved = torch.from_numpy(slot < 2).to(DEV)
+    for k in GROUPS:
+        got, want = new[k].detach(), params[k].detach()[src_d]
+        assert got.shape == want.shape, k
+        if k in ("xyz", "scaling"):
+            assert torch.equal(got[moved], want[moved]), k
+        else:
+            assert torch.equal(got, want), k
+        st = opt.state[new[k]]
+        assert st["step"] is moments[k][2] and float(st["step"]) == 7.0
+        for j, m in enumerate(("exp_avg", "exp_avg_sq")):
+            w = moments[k][j][src_d]
+            w[~old_d] = 0.0
+            assert torch.equal(st[m], w), (k, m)
+    for k in STATS:
+        if stats is None:
+            assert new_stats[k].shape == ((len(src),) if k == "max_radii2D" else (len(src), 1)), k
+            assert not new_stats[k].any(), k
+        else:
+            assert torch.equal(new_stats[k], stats[k][src_d]), k
+
+
+@pytest.mark.parametrize("size", [None, 20])
+@pytest.mark.parametrize("n", SWEEP_N)
+def test_densify_sweep_against_the_restatement(n, size):
+    from gsplat_mi355 import densify
+    from oracle import densify_ref as dr
+    host, params, opt, stats = _sweep_state(n)
+    want = dr.densify_and_prune(host["scaling"], host["opacity"], host["xyz_gradient_accum"], host["denom"],
+                                max_screen_size=size, **SWEEP_KW)
+    plan = densify.plan_densify(params, stats, max_screen_size=size, **SWEEP_KW)
+    masks = {k: v.cpu().numpy() for k, v in plan.masks().items()}
+    for k in ("clone", "split", "keep", "prune", "child_prune"):
+        assert np.array_equal(masks[k], want[k]), (n, size, k)
+    assert plan.n_new == want["n_new"]
+    # the row map, before anything gathers by it
+    src, slot = (t.cpu().numpy() for t in plan.row_map())
+    assert np.array_equal(slot, want["slot"]), (n, size, "slot")
+    assert np.array_equal(src, want["src"]), (n, size, "src")
+    moments = {k: (opt.state[params[k]]["exp_avg"], opt.state[params[k]]["exp_avg_sq"], opt.state[params[k]]["step"])
+               for k in GROUPS}
+    noise = torch.randn((n, 2, 3), device=DEV, generator=torch.Generator(device=DEV).manual_seed(n + 1))
+    new, new_stats = densify.apply_plan(plan, params, opt, stats, noise)
+    torch.cuda.synchronize()
+    _check_rows(new, opt, params, moments, src, slot, new_stats=new_stats)
+    child = slot >= 2
+    pos, scl = dr.children(host["xyz"], host["scaling"], host["rotation"], noise.cpu().numpy(), src, slot)
+    ch = torch.from_numpy(child).to(DEV)
+    assert _close(new["xyz"].detach()[ch].cpu().numpy(), pos) and _close(new["scaling"].detach()[ch].cpu().numpy(), scl)
+
+
+def _prune_masks(n):
+    masks = {"every third kept": np.arange(n) % 3 != 0, "last row": np.arange(n) == n - 1}
+    if n > 257 * 1024:
+        m = np.zeros(n, bool)
+        m[1000:1000 + 257 * 1024 + 7] = True  # a run over more than a scan round
+        masks["run of 257 blocks"] = m
+    return masks
+
+
+@pytest.mark.parametrize("n", SWEEP_N)
+def test_prune_points_sweep_against_the_restatement(n):
+    from gsplat_mi355 import densify
+    from oracle import densify_ref as dr
+    for name, mask in _prune_masks(n).items():
+        _, params, opt, stats = _sweep_state(n)
+        src, slot = dr.prune_points(mask)
+        plan = densify.plan_prune(params, torch.from_numpy(mask).to(DEV))
+        assert plan.n_new == len(src), name
+        got_src, got_slot = (t.cpu().numpy() for t in plan.row_map())
+        assert np.array_equal(got_slot, slot) and np.array_equal(got_src, src), (n, name)
+        moments = {k: (opt.state[params[k]]["exp_avg"], opt.state[params[k]]["exp_avg_sq"], opt.state[params[k]]["step"])
+                   for k in GROUPS}
+        new, new_stats = densify.apply_plan(plan, params, opt, stats)
+        torch.cuda.synchronize()
+        _check_rows(new, opt, params, moments, src, slot, new_stats=new_stats, stats=stats)
+
+
+@pytest.mark.parametrize("n", [1025, 1100001])
+def test_reset_opacity_sweep_against_the_restatement(n):
+    from gsplat_mi355 import densify
+    from oracle import densify_ref as dr
+    host, params, opt, _ = _sweep_state(n)
+    steps = opt.state[params["opacity"]]["step"]
+    out = densify.reset_opacity(params, opt)
+    torch.cuda.synchronize()
+    assert _close(out["opacity"].detach().cpu().numpy(), dr.reset_opacity(host["opacity"]))
+    st = opt.state[out["opacity"]]
+    assert st["step"] is steps and not st["exp_avg"].any() and not st["exp_avg_sq"].any()
+    assert st["exp_avg"].shape == st["exp_avg_sq"].shape == (n, 1)
