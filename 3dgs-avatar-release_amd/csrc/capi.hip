@@ -802,6 +802,38 @@ int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, flo
     return launch_reset_opacity(N, opacity_in, opacity_out, exp_avg, exp_avg_sq, (hipStream_t)stream);
 }
 
+// ---- AIAP regularisers (aiap.hip).  M = N (K - 1) pairs stay below 2^31 (the sort and the adjacency index 32-bit words)
+static bool aiap_shape_ok(int32_t N, int32_t K, int32_t n_sets) {
+    return N >= 1 && K >= 2 && K <= 8 && (n_sets == 1 || n_sets == 2) && (int64_t)N * (K - 1) < ((int64_t)1 << 31);
+}
+static bool aiap_sets_ok(int32_t n_sets, const GsAiapSet* sets, bool forward) {
+    if (!sets) return false;
+    for (int k = 0; k < n_sets; k++) {
+        const GsAiapSet& s = sets[k];
+        if ((s.D != 3 && s.D != 6) || !s.xc || !s.xd || (forward && !s.loss)) return false;
+    }
+    return true;
+}
+int gs_aiap_workspace_bytes(int32_t N, int32_t K, int32_t n_sets, size_t* out) {
+    if (!out || !aiap_shape_ok(N, K, n_sets)) return GS_E_BAD_ARG;
+    *out = aiap_workspace_bytes(N, K);
+    return GS_OK;
+}
+int gs_aiap_forward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, true)) return GS_E_BAD_ARG;
+    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
+    return launch_aiap_forward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
+}
+int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets,
+                     const void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, false)) return GS_E_BAD_ARG;
+    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
+    return launch_aiap_backward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

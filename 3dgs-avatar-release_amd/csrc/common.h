@@ -533,6 +533,11 @@ int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_
 int launch_densify_apply(int N, int N_new, const void* workspace, int n, const GsDensifyTensor* tensors,
                          const float* scaling, const float* rotation, const float* noise, hipStream_t s);
 int launch_reset_opacity(int N, const float* in, float* out, float* exp_avg, float* exp_avg_sq, hipStream_t s);
+// AIAP regularisers (aiap.hip): up to two (xc, xd) sets sharing one neighbour list; the spec is at the top of aiap.hip
+size_t aiap_workspace_bytes(int N, int K);
+int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, void* workspace, hipStream_t s);
+int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
+                         hipStream_t s);
 
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,

@@ -47,7 +47,8 @@ extern "C" {
  *                          empty: read the count afterwards, outside the graph)
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
- *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity
+ *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
+ *   gs_aiap_forward, gs_aiap_backward
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -372,6 +373,34 @@ int gs_densify_apply(int32_t N, int32_t N_new, const void* workspace, size_t wor
                      void* stream);
 int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, float* exp_avg, float* exp_avg_sq,
                      void* stream);
+
+/* ---- as-isometric-as-possible regularisers (utils/loss_utils.py:69-102; train.py:163-171): per set,
+ * L = mean over the pairs (i, idx[i, k]), k = 1 .. K-1, of | |xc_i - xc_j| - |xd_i - xd_j| |, and its gradients w.r.t.
+ * xc and xd.  The full semantics are spelled out at the top of csrc/aiap.hip.  One or two sets share one neighbour list
+ * (full_aiap_loss: positions, D = 3, and strip_symmetric covariances, D = 6).
+ * gs_aiap_forward: writes every set's loss[0] (device float) and builds in `workspace` (gs_aiap_workspace_bytes(N, K,
+ *   n_sets) bytes) the stable reverse adjacency of idx that gs_aiap_backward reuses: call the backward with the same
+ *   N, K, idx, sets and workspace.  idx is [N, K] int64, contiguous; a value of columns 1 .. K-1 outside [0, N) is never
+ *   dereferenced (the pair adds nothing) and is counted: workspace word 0 (uint32) holds the count after the forward.
+ * gs_aiap_backward: writes every non-NULL dL_dxc / dL_dxd [N, D] row exactly once (no atomics: bitwise reproducible),
+ *   scaled by the device scalar dL_dloss (NULL = 1).
+ * Rows are read and written with 4-byte accesses: xc, xd and the gradients need only fp32 alignment.
+ * GS_E_BAD_ARG: N < 1, K < 2, K > 8, n_sets not 1 or 2, a D not 3 or 6, N (K - 1) >= 2^31, or a NULL required pointer
+ * (idx, sets, workspace, xc, xd; loss in the forward).  GS_E_WORKSPACE: the workspace is too small. ---- */
+typedef struct GsAiapSet {
+    const float* xc;       /* [N, D] canonical */
+    const float* xd;       /* [N, D] deformed */
+    int32_t D;             /* 3 or 6 */
+    float* loss;           /* forward: device float */
+    const float* dL_dloss; /* backward: device float, NULL = 1 */
+    float* dL_dxc;         /* backward: [N, D] or NULL (not wanted) */
+    float* dL_dxd;         /* backward: [N, D] or NULL */
+} GsAiapSet;
+int gs_aiap_workspace_bytes(int32_t N, int32_t K, int32_t n_sets, size_t* out);
+int gs_aiap_forward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets,
+                     const void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`:
  *  geom:    0 depths f32[P]        1 tiles_touched u32[P]   2 splat records f32[P,12]
