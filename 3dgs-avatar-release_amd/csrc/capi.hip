@@ -834,6 +834,65 @@ int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, c
     return launch_aiap_backward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
 }
 
+// ---- hash-grid encoding (hashgrid.hip)
+static bool hg_aligned(const void* p, int F) { return p == nullptr || ((uintptr_t)p % (uintptr_t)(4 * (F < 4 ? F : 4))) == 0; }
+int gs_hashgrid_levels(const GsHashGrid* grid, int32_t* offsets, float* scales, int32_t* resolutions, int32_t* n_params) {
+    if (!grid) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    for (int l = 0; l <= t.L; l++) {
+        if (offsets) offsets[l] = (int32_t)t.off[l];
+        if (l == t.L) break;
+        if (scales) scales[l] = t.scale[l];
+        if (resolutions) resolutions[l] = (int32_t)t.res[l];
+    }
+    if (n_params) *n_params = (int32_t)(t.off[t.L] * (uint32_t)t.F);
+    return GS_OK;
+}
+// the sort numbers the 8 L N (point, level, corner) pairs with 32-bit words
+static bool hg_pairs_fit(const HgTable& t, int32_t N) { return (int64_t)8 * t.L * N < ((int64_t)1 << 31); }
+int gs_hashgrid_workspace_bytes(const GsHashGrid* grid, int32_t N, size_t* out) {
+    if (!grid || !out || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if (!hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
+    *out = hashgrid_workspace_bytes(t, N);
+    return GS_OK;
+}
+int gs_hashgrid_forward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, float* out, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!grid || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if ((int64_t)N * t.L >= ((int64_t)1 << 31)) return GS_E_TOO_LARGE;
+    if (N == 0 || !out) return GS_OK;
+    if (!x || !params || !hg_aligned(params, t.F) || !hg_aligned(out, t.F) || !hg_aligned(x, 1)) return GS_E_BAD_ARG;
+    return launch_hashgrid_forward(t, N, x, params, out, (hipStream_t)stream);
+}
+int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, const float* dL_dout,
+                         float* dL_dx, float* dL_dparams, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!grid || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if (dL_dparams && !hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
+    if (!dL_dparams && (N == 0 || !dL_dx)) return GS_OK;
+    if (N > 0 && (!x || !dL_dout || (dL_dx && !params))) return GS_E_BAD_ARG;
+    if (!hg_aligned(params, t.F) || !hg_aligned(dL_dout, t.F) || !hg_aligned(dL_dparams, t.F) || !hg_aligned(x, 1) ||
+        !hg_aligned(dL_dx, 1))
+        return GS_E_BAD_ARG;
+    if (dL_dparams) {
+        if (!workspace) return GS_E_BAD_ARG;
+        if (workspace_bytes < hashgrid_workspace_bytes(t, N)) return GS_E_WORKSPACE;
+    }
+    return launch_hashgrid_backward(t, N, x, params, dL_dout, N > 0 ? dL_dx : nullptr, dL_dparams, workspace,
+                                    (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

@@ -539,6 +539,18 @@ int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const Gs
 int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
                          hipStream_t s);
 
+// multiresolution hash-grid encoding (hashgrid.hip; the spec is at its top).  HgTable: the level table, passed to the
+// kernels by value (computed on the host by hashgrid_table, the one source of the integer decisions)
+struct HgTable {
+    int L, F;
+    float scale[GS_HASHGRID_MAX_LEVELS];
+    uint32_t res[GS_HASHGRID_MAX_LEVELS], size[GS_HASHGRID_MAX_LEVELS], off[GS_HASHGRID_MAX_LEVELS + 1];
+};
+int hashgrid_table(const GsHashGrid* g, HgTable* t);
+size_t hashgrid_workspace_bytes(const HgTable& t, int N);
+int launch_hashgrid_forward(const HgTable& t, int N, const float* x, const float* params, float* out, hipStream_t s);
+int launch_hashgrid_backward(const HgTable& t, int N, const float* x, const float* params, const float* dL_dout,
+                             float* dL_dx, float* dL_dparams, void* workspace, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

@@ -42,7 +42,8 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_build_covariance", "gs_build_covariance_backward", "gs_sh2rgb", "gs_sh2rgb_backward", "knn_points", "gs_densify_stats", "gs_adam_step",
            "gs_opacity_image", "gs_backward_with_opacity", "gs_tuning", "gs_profile_reserve", "gs_image_bytes_for", "gs_backward_with_second", "gs_clock_probe", "gs_pair_stats", "gs_xcc_probe",
            "gs_densify_workspace_bytes", "gs_densify_plan", "gs_densify_apply", "gs_reset_opacity",
-           "gs_aiap_workspace_bytes", "gs_aiap_forward", "gs_aiap_backward"]
+           "gs_aiap_workspace_bytes", "gs_aiap_forward", "gs_aiap_backward",
+           "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -73,6 +74,14 @@ class GsDensifyTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsDensifyTen
 class GsAiapSet(ctypes.Structure):  # include/gsplat_mi355.h: GsAiapSet
     _fields_ = [("xc", c_void_p), ("xd", c_void_p), ("D", c_int32), ("loss", c_void_p), ("dL_dloss", c_void_p),
                 ("dL_dxc", c_void_p), ("dL_dxd", c_void_p)]
+
+
+GS_HASHGRID_MAX_LEVELS = 32  # include/gsplat_mi355.h
+
+
+class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
+    _fields_ = [("n_levels", c_int32), ("n_features_per_level", c_int32), ("log2_hashmap_size", c_int32),
+                ("base_resolution", c_int32), ("per_level_scale", c_float)]
 
 
 _lock = threading.Lock()
@@ -143,6 +152,11 @@ def load():
         L.gs_aiap_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, POINTER(c_size_t)]
         L.gs_aiap_forward.argtypes = [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]
         L.gs_aiap_backward.argtypes = [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]
+        L.gs_hashgrid_levels.argtypes = [POINTER(GsHashGrid), c_void_p, c_void_p, c_void_p, c_void_p]
+        L.gs_hashgrid_workspace_bytes.argtypes = [POINTER(GsHashGrid), c_int32, POINTER(c_size_t)]
+        L.gs_hashgrid_forward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.gs_hashgrid_backward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

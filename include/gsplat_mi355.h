@@ -48,7 +48,7 @@ extern "C" {
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
- *   gs_aiap_forward, gs_aiap_backward
+ *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -401,6 +401,36 @@ int gs_aiap_forward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, co
                     size_t workspace_bytes, void* stream);
 int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets,
                      const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- multiresolution hash-grid encoding (tcnn.Encoding(3, {"otype": "HashGrid", ...}) of the reference's non-rigid
+ * deformer, models/network_utils.py:329-343): 3-D input, linear interpolation, fp32 parameters and arithmetic.  The full
+ * semantics (level table, cell, corner index, weights, gradients) are spelled out at the top of csrc/hashgrid.hip.
+ * gs_hashgrid_levels: host only (no device, no stream).  Fills offsets[L + 1] (the first table row of every level, in rows
+ *   of F features; offsets[L] = the number of rows), scales[L] (the float32 scale_l the kernels use), resolutions[L] and
+ *   *n_params = offsets[L] * F; any of the four may be NULL.
+ * gs_hashgrid_forward: out [N, L F] fp32, row-major, from x [N, 3] fp32 and params [n_params] fp32.
+ * gs_hashgrid_backward: from dL_dout [N, L F]: dL_dx [N, 3] (gather only: every row written once) and dL_dparams
+ *   [n_params] (every element written exactly once, 0 where no point reaches it; no atomics: bitwise reproducible).
+ *   Either may be NULL (not wanted); `workspace` (gs_hashgrid_workspace_bytes) is needed only with dL_dparams, params
+ *   only with dL_dx.  The forward and the backward are independent: the backward keeps nothing from the forward.
+ * x needs fp32 alignment; params, out, dL_dout and dL_dparams need 4 min(F, 4)-byte alignment.
+ * GS_E_BAD_ARG: a NULL required pointer or grid, N < 0, a misaligned pointer, or a config outside: 1 <= n_levels <=
+ * GS_HASHGRID_MAX_LEVELS, n_features_per_level in {1, 2, 4, 8}, 1 <= log2_hashmap_size <= 30, base_resolution >= 1,
+ * 1 <= per_level_scale <= 1e4.  GS_E_TOO_LARGE: n_params >= 2^31 or a level's resolution beyond 32 bits; N L >= 2^31 (forward);
+ * 8 L N >= 2^31 with dL_dparams (the sort's 32-bit pair index).  GS_E_WORKSPACE: the workspace is too small. ---- */
+#define GS_HASHGRID_MAX_LEVELS 32
+typedef struct GsHashGrid {
+    int32_t n_levels;             /* L */
+    int32_t n_features_per_level; /* F */
+    int32_t log2_hashmap_size;    /* T */
+    int32_t base_resolution;      /* N0 */
+    float per_level_scale;        /* b (float32, as tcnn's host code reads it) */
+} GsHashGrid;
+int gs_hashgrid_levels(const GsHashGrid* grid, int32_t* offsets, float* scales, int32_t* resolutions, int32_t* n_params);
+int gs_hashgrid_workspace_bytes(const GsHashGrid* grid, int32_t N, size_t* out);
+int gs_hashgrid_forward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, float* out, void* stream);
+int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, const float* dL_dout,
+                         float* dL_dx, float* dL_dparams, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`:
  *  geom:    0 depths f32[P]        1 tiles_touched u32[P]   2 splat records f32[P,12]
