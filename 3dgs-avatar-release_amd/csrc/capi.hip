@@ -893,6 +893,61 @@ int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, cons
                                     (hipStream_t)stream);
 }
 
+// ---- linear blend skinning (skinning.hip)
+static bool skin_a16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static bool skin_a4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+static bool skin_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX || kind == GS_SKIN_WEIGHTS; }
+int gs_skin_weights_forward(int32_t N, int32_t kind, const float* logits, float* weights, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!logits || !weights || !skin_a16(logits) || !skin_a16(weights)) return GS_E_BAD_ARG;
+    return launch_skin_weights_forward(N, kind, logits, weights, (hipStream_t)stream);
+}
+int gs_skin_weights_backward(int32_t N, int32_t kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
+                             void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!logits || !dL_dweights || !dL_dlogits || !skin_a16(logits) || !skin_a16(dL_dweights) || !skin_a16(dL_dlogits))
+        return GS_E_BAD_ARG;
+    return launch_skin_weights_backward(N, kind, logits, dL_dweights, dL_dlogits, (hipStream_t)stream);
+}
+int gs_skinning_workspace_bytes(int32_t N, size_t* out) {
+    if (!out || N < 0) return GS_E_BAD_ARG;
+    *out = skinning_workspace_bytes(N);
+    return GS_OK;
+}
+int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                        float* xyz_out, float* rotation_out, float* T_fwd, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!w || !tfs || !xyz || !rotation || !xyz_out || !rotation_out || !T_fwd) return GS_E_BAD_ARG;
+    if (!skin_a16(w) || !skin_a16(tfs) || !skin_a16(rotation) || !skin_a16(xyz_out) || !skin_a16(rotation_out) ||
+        !skin_a16(T_fwd) || !skin_a4(xyz))
+        return GS_E_BAD_ARG;
+    return launch_skinning_forward(N, kind, w, tfs, xyz, rotation, xyz_out, rotation_out, T_fwd, (hipStream_t)stream);
+}
+int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                         const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
+                         float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!w || !tfs || !xyz || !rotation) return GS_E_BAD_ARG;
+    if (!skin_a16(w) || !skin_a16(tfs) || !skin_a16(rotation) || !skin_a4(xyz) || !skin_a4(dL_dxyz_out) ||
+        !skin_a4(dL_drotation_out) || !skin_a16(dL_dw) || !skin_a4(dL_dtfs) || !skin_a4(dL_dxyz) || !skin_a16(dL_drotation))
+        return GS_E_BAD_ARG;
+    if (dL_dtfs) {
+        if (!workspace || !skin_a16(workspace)) return GS_E_BAD_ARG;
+        if (workspace_bytes < skinning_workspace_bytes(N)) return GS_E_WORKSPACE;
+    }
+    if (!dL_dw && !dL_dtfs && !dL_dxyz && !dL_drotation) return GS_OK;
+    return launch_skinning_backward(N, kind, w, tfs, xyz, rotation, dL_dxyz_out, dL_drotation_out, dL_dw, dL_dtfs, dL_dxyz,
+                                    dL_drotation, workspace, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

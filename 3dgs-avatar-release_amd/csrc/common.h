@@ -551,6 +551,16 @@ size_t hashgrid_workspace_bytes(const HgTable& t, int N);
 int launch_hashgrid_forward(const HgTable& t, int N, const float* x, const float* params, float* out, hipStream_t s);
 int launch_hashgrid_backward(const HgTable& t, int N, const float* x, const float* params, const float* dL_dout,
                              float* dL_dx, float* dL_dparams, void* workspace, hipStream_t s);
+// linear blend skinning of the rigid deformer (skinning.hip; the spec is at its top)
+size_t skinning_workspace_bytes(int N);
+int launch_skin_weights_forward(int N, int kind, const float* logits, float* weights, hipStream_t s);
+int launch_skin_weights_backward(int N, int kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
+                                 hipStream_t s);
+int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
+                            float* xyz_out, float* rot_out, float* T_fwd, hipStream_t s);
+int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
+                             const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
+                             void* workspace, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

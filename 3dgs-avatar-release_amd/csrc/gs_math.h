@@ -39,6 +39,28 @@ __device__ __forceinline__ void quat_to_R(const float4 q, float R[3][3]) {
     R[2][2] = 1.f - 2.f * (x * x + y * y);
 }
 
+// q = r / |r| without an epsilon, as utils/general_utils.py:87-91; *norm = |r|
+__device__ __forceinline__ float4 quat_normalize(const float4 r, float* norm) {
+    const float n = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
+    *norm = n;
+    return make_float4(r.x / n, r.y / n, r.z / n, r.w / n);
+}
+
+// dL/dr of the raw quaternion r from dL/dR of R = quat_to_R(q), q = r / |r| (quat_normalize's q and norm); the same
+// expressions as build_cov_bwd_kernel's (prepass.hip keeps its own copy: compiled with FMA contraction, its code would
+// not stay the same instruction for instruction)
+__device__ __forceinline__ float4 quat_R_backward(const float4 q, float n, const float dR[3][3]) {
+    const float r = q.x, x = q.y, y = q.z, z = q.w;
+    float gq[4];
+    gq[0] = 2 * z * (dR[1][0] - dR[0][1]) + 2 * y * (dR[0][2] - dR[2][0]) + 2 * x * (dR[2][1] - dR[1][2]);
+    gq[1] = 2 * y * (dR[0][1] + dR[1][0]) + 2 * z * (dR[0][2] + dR[2][0]) + 2 * r * (dR[2][1] - dR[1][2]) - 4 * x * (dR[2][2] + dR[1][1]);
+    gq[2] = 2 * x * (dR[0][1] + dR[1][0]) + 2 * r * (dR[0][2] - dR[2][0]) + 2 * z * (dR[2][1] + dR[1][2]) - 4 * y * (dR[2][2] + dR[0][0]);
+    gq[3] = 2 * r * (dR[1][0] - dR[0][1]) + 2 * x * (dR[0][2] + dR[2][0]) + 2 * y * (dR[2][1] + dR[1][2]) - 4 * z * (dR[1][1] + dR[0][0]);
+    // through q = r_in / |r_in|:  d/dr_in = (gq - q (q . gq)) / |r_in|
+    const float dot = r * gq[0] + x * gq[1] + y * gq[2] + z * gq[3];
+    return make_float4((gq[0] - r * dot) / n, (gq[1] - x * dot) / n, (gq[2] - y * dot) / n, (gq[3] - z * dot) / n);
+}
+
 __device__ __forceinline__ void cov3d_from_scale_rot(const float3 scale, float mod, const float4 q, float* c6) {
     float R[3][3];
     quat_to_R(q, R);

@@ -43,7 +43,9 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_opacity_image", "gs_backward_with_opacity", "gs_tuning", "gs_profile_reserve", "gs_image_bytes_for", "gs_backward_with_second", "gs_clock_probe", "gs_pair_stats", "gs_xcc_probe",
            "gs_densify_workspace_bytes", "gs_densify_plan", "gs_densify_apply", "gs_reset_opacity",
            "gs_aiap_workspace_bytes", "gs_aiap_forward", "gs_aiap_backward",
-           "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward"]
+           "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward",
+           "gs_skin_weights_forward", "gs_skin_weights_backward", "gs_skinning_workspace_bytes", "gs_skinning_forward",
+           "gs_skinning_backward"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -77,6 +79,10 @@ class GsAiapSet(ctypes.Structure):  # include/gsplat_mi355.h: GsAiapSet
 
 
 GS_HASHGRID_MAX_LEVELS = 32  # include/gsplat_mi355.h
+
+
+GS_SKIN_BONES = 24  # include/gsplat_mi355.h
+GS_SKIN_HIERARCHICAL, GS_SKIN_SOFTMAX, GS_SKIN_WEIGHTS = 0, 1, 2
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -157,6 +163,13 @@ def load():
         L.gs_hashgrid_forward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_hashgrid_backward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_void_p]
+        L.gs_skin_weights_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+        L.gs_skin_weights_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.gs_skinning_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
+        L.gs_skinning_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]
+        L.gs_skinning_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

@@ -48,7 +48,8 @@ extern "C" {
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
- *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward
+ *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
+ *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -431,6 +432,37 @@ int gs_hashgrid_workspace_bytes(const GsHashGrid* grid, int32_t N, size_t* out);
 int gs_hashgrid_forward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, float* out, void* stream);
 int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, const float* dL_dout,
                          float* dL_dx, float* dL_dparams, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- linear blend skinning of the rigid deformer (models/deformer/rigid.py: SkinningField.forward with its
+ * hierarchical_softmax / F.softmax, SMPLNN.forward with given weights; build_rotation at utils/general_utils.py:87-108).
+ * The full semantics (the three weight kinds, T_fwd, x_bar, R_bar and every gradient) are spelled out at the top of
+ * csrc/skinning.hip.  All arrays are fp32, row-major, contiguous.  `w` is [N, 25] logits (GS_SKIN_HIERARCHICAL), [N, 24]
+ * logits (GS_SKIN_SOFTMAX) or [N, 24] weights (GS_SKIN_WEIGHTS); tfs [24, 4, 4] (camera.bone_transforms); xyz [N, 3];
+ * rotation [N, 4] raw (w,x,y,z) quaternions (normalised inside, no epsilon).
+ * gs_skin_weights_forward / _backward: the activation alone (kind 0 or 1): weights [N, 24] from logits, and dL_dlogits
+ *   from dL_dweights [N, 24].
+ * gs_skinning_forward: xyz_out [N, 3] = T[:3,:3] x + T[:3,3], rotation_out [N, 3, 3] = T[:3,:3] R(q), T_fwd [N, 4, 4] =
+ *   sum_j W_j tfs_j.
+ * gs_skinning_backward: from dL_dxyz_out [N, 3] and dL_drotation_out [N, 3, 3] (either NULL = zero): dL_dw (shaped as
+ *   w), dL_dtfs [24, 4, 4] (rows 3 are 0), dL_dxyz [N, 3] (the direct term T[:3,:3]^T g) and dL_drotation [N, 4]; any
+ *   of the four may be NULL (not wanted).  Every row is written exactly once and dL_dtfs is summed in a fixed order
+ *   (no atomics: bitwise reproducible).  `workspace` (gs_skinning_workspace_bytes(N)) is needed only with dL_dtfs.  The
+ *   backward recomputes everything from its inputs: it keeps nothing from the forward.
+ * Alignment: w, dL_dw, weights, dL_dweights, dL_dlogits, tfs, rotation, rotation_out, dL_drotation, xyz_out and T_fwd
+ * need 16 bytes (16-byte accesses); the other arrays fp32 alignment.  N = 0 touches nothing (dL_dtfs included).
+ * GS_E_BAD_ARG (before any HIP call): N < 0, an unknown kind (GS_SKIN_WEIGHTS in gs_skin_weights_*), a NULL required
+ * pointer or a misaligned one.  GS_E_WORKSPACE: the workspace is smaller than gs_skinning_workspace_bytes(N). ---- */
+#define GS_SKIN_BONES 24
+enum { GS_SKIN_HIERARCHICAL = 0 /* 25 logits */, GS_SKIN_SOFTMAX = 1 /* 24 logits */, GS_SKIN_WEIGHTS = 2 /* 24 weights */ };
+int gs_skin_weights_forward(int32_t N, int32_t kind, const float* logits, float* weights, void* stream);
+int gs_skin_weights_backward(int32_t N, int32_t kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
+                             void* stream);
+int gs_skinning_workspace_bytes(int32_t N, size_t* out);
+int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                        float* xyz_out, float* rotation_out, float* T_fwd, void* stream);
+int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                         const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
+                         float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`:
  *  geom:    0 depths f32[P]        1 tiles_touched u32[P]   2 splat records f32[P,12]
