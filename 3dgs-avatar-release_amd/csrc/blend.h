@@ -30,10 +30,27 @@ struct Staged {
 // minimum sits on one of the four edges, where it is a clamped 1-D parabola) against
 // 2 tau = 2 ln(255 opacity) (+ slack).  alpha >= 1/255 <=> q <= 2 ln(255 opacity); the test keeps a
 // 1e-3 (log2) slack plus a relative 1e-4, so every pair it drops would fail the per-pixel alpha test.
-__device__ __forceinline__ float edge_min(float a, float b2, float c, float xf, float y0, float y1) {
-    // min over y in [y0, y1] of a xf^2 + b2 xf y + c y^2   (b2 = 2 B)
-    const float ys = fminf(fmaxf(-0.5f * b2 * xf / c, y0), y1);
-    return a * xf * xf + (b2 * xf + c * ys) * ys;
+//
+// The test holds NO division (it runs once per list entry and quadrant wave, in front of a loop bound by VALU issue; a
+// correctly rounded quotient is ~11 instructions, and the exact form had five of them):
+//   * the parabola's vertex on an edge is ys = clamp(k xf, y0, y1) with k = -B / c: ONE approximate reciprocal
+//     (v_rcp_f32, 1 ulp) per orientation, shared by the orientation's two edges.  An inexact ys does not leave the edge;
+//     it moves the evaluated point by d = |ys| e along it (e ~ 3 x 2^-23: the reciprocal and two roundings) and RAISES the
+//     value, by exactly c d^2 = (c ys^2) e^2 -- second order.  Against the minimum itself, xf^2 det / c at an unclamped
+//     vertex, that is (B^2 / det) e^2 <= (A C / det) e^2 < 2.7e5 x 1.3e-13 = 4e-8 relative (A C / det < 2.7e5 is what
+//     `rel < 0.5` below demands): three orders of magnitude inside the 1e-4 relative slack.  A clamped vertex is y0 or y1
+//     itself (v_med3_f32 is exact);
+//   * the decision is one compare of the minimum against a limit that depends on the Gaussian alone:
+//     qmin (1 - rel) - 1e-3 <= 2 tau  <=>  qmin <= (2 tau + 1e-3) / (1 - rel)   (0.5 < 1 - rel <= 1),
+//     lim = (2 tau + 1e-3) rcp(1 - rel) (1 + 2^-20).  The last factor pays for what the rewrite rounds differently: two
+//     approximate reciprocals (rcp(det) enters through rel < 0.5 scaled by 1.9e-6, rcp(1 - rel) in full: 2^-23) and three
+//     products (3 x 2^-24) -- under 2^-21 in all, so lim is never below the exact quotient, and 2^-20 = 1e-6 is a
+//     hundredth of the relative slack that is there to be used up.
+// NaN (0 x inf from a subnormal C) fails `qmin > lim` and keeps the entry.
+// min over y in [y0, y1] of axx + b2x y + c y^2, the edge at xf:  axx = a xf^2, b2x = 2 B xf, kx = -(B / c) xf
+__device__ __forceinline__ float edge_min(float axx, float b2x, float c, float kx, float y0, float y1) {
+    const float ys = __builtin_amdgcn_fmed3f(kx, y0, y1);
+    return axx + (b2x + c * ys) * ys;
 }
 __device__ __forceinline__ bool stage_entry_quad(const float4 r0, const float4 r1, const float4 r2, int QX0, int QY0,
                                                  Staged& s) {
@@ -49,13 +66,17 @@ __device__ __forceinline__ bool stage_entry_quad(const float4 r0, const float4 r
             const float y0 = (float)QY0 - gy, y1 = y0 + 7.f;
             const bool inside = (x0 <= 0.f) && (x1 >= 0.f) && (y0 <= 0.f) && (y1 >= 0.f);
             const float b2 = 2.f * B;
-            const float qmin = fminf(fminf(edge_min(A, b2, C, x0, y0, y1), edge_min(A, b2, C, x1, y0, y1)),
-                                     fminf(edge_min(C, b2, A, y0, x0, x1), edge_min(C, b2, A, y1, x0, x1)));
+            const float ky = -B * __builtin_amdgcn_rcpf(C), kx = -B * __builtin_amdgcn_rcpf(A);  // vertex slopes: y = ky x, x = kx y
+            const float axx0 = A * x0 * x0, axx1 = A * x1 * x1, cyy0 = C * y0 * y0, cyy1 = C * y1 * y1;
+            const float qmin = fminf(fminf(edge_min(axx0, b2 * x0, C, ky * x0, y0, y1), edge_min(axx1, b2 * x1, C, ky * x1, y0, y1)),
+                                     fminf(edge_min(cyy0, b2 * y0, A, kx * y0, x0, x1), edge_min(cyy1, b2 * y1, A, kx * y1, x0, x1)));
             // relative slack: 1e-4, plus the rounding of a form whose terms cancel (long thin Gaussians): ~2^-24 A C / det
             // per operation (gs_math.h: snug_half_widths); when the bound says nothing the entry is kept
-            const float detc = A * C - B * B;
-            const float rel = 1e-4f + (A * C) / detc * 1.9073486e-6f;
-            hit = inside || !(detc > 0.f) || !(rel < 0.5f) || (qmin * (1.0f - rel) - 1e-3f <= two_tau);
+            const float AC = A * C;
+            const float detc = AC - B * B;
+            const float rel = 1e-4f + AC * __builtin_amdgcn_rcpf(detc) * 1.9073486e-6f;
+            const float lim = (two_tau + 1e-3f) * __builtin_amdgcn_rcpf(1.0f - rel) * 1.00000095f;  // (1 + 2^-20)
+            hit = inside || !(detc > 0.f) || !(rel < 0.5f) || !(qmin > lim);
         }
     }
     s.a = make_float4(gx, gy, (-0.5f * LOG2E_F) * A, -LOG2E_F * B);
@@ -69,6 +90,20 @@ __device__ __forceinline__ void stage_entry_convert(const float4 r0, const float
     s.a = make_float4(r0.x, r0.y, (-0.5f * LOG2E_F) * r0.z, -LOG2E_F * r0.w);
     s.b = make_float4((-0.5f * LOG2E_F) * r1.x, r1.y, 0.f, 0.f);
     s.c = make_float4(r1.z, r1.w, r2.x, 0.f);
+}
+
+// The inner loop's marks (render_fwd.hip: blend / step): where a pair is blended, the loop's LDS address register is
+// kept -- for the even entries of a run the entry's own address, for the odd ones the address 48 bytes past it.  So
+// entry j of the batch (staged at sp0 + 48 j) leaves sp0 + 48 j in mark_e or sp0 + 48 (j + 1) in mark_o, and the last
+// blended entry of the batch, as a 1-based index into it, is max(mark_e + 48, mark_o) - sp0 over 48: ONE decode for
+// both marks (48-byte entries: x / 48 = x * 43691 >> 21 for x < 2^15).  "No entry yet" is the pair of marks that decodes to 0.
+// (render_quadrant_1 only: in render_chunk, at 80 VGPRs, marks that start from sp0 cost two spilled registers -- it keeps
+// its two decodes from 0xFFFFFFFF.)
+__device__ __forceinline__ uint32_t mark_none_even(uint32_t sp0) { return sp0 - 48u; }
+__device__ __forceinline__ uint32_t mark_none_odd(uint32_t sp0) { return sp0; }
+__device__ __forceinline__ uint32_t marks_last_entry(uint32_t mark_e, uint32_t mark_o, uint32_t sp0) {
+    const uint32_t d = max(mark_e - sp0 + 48u, mark_o - sp0);  // (both >= 0: marks only ever move up from "none")
+    return (d * 43691u) >> 21;
 }
 
 // ---- DPP helpers (cross-lane moves without LDS) ----

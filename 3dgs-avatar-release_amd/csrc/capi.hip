@@ -996,6 +996,7 @@ int gs_binning_field(void* binning, int64_t D, int32_t W, int32_t H, int32_t fie
     char* b = (char*)binning;
     switch (field) {
         case 0: *out = b + B.point_list; break;  // (the tile id of every entry follows from the image state's ranges)
+        case 1: *out = b + B.qlist; break;       // quadrant (tile t, q): [4 ranges[t].x + q n_t, ... + qcount[t][q])
         default: return GS_E_BAD_ARG;
     }
     return GS_OK;

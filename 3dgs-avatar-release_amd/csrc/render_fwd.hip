@@ -229,7 +229,7 @@ __device__ __forceinline__ void render_quadrant_1(const FwdArgs& A, const int ti
         };
         // even entries of a run are evaluated with sp at their own address, odd ones with sp 48 bytes past theirs
         const uint32_t sp0 = (uint32_t)(uintptr_t)sp;
-        uint32_t mark_e = 0xFFFFFFFFu, mark_o = 0xFFFFFFFFu;  // (no LDS address)
+        uint32_t mark_e = mark_none_even(sp0), mark_o = mark_none_odd(sp0);  // (blend.h: marks_last_entry)
         // entries [j0, j1) of the batch (sp stands at entry j0, and at entry j1 afterwards)
         auto run = [&](const int j0, const int j1) {
             float4 a0 = ld_a(0), c0 = ld_c(0);
@@ -264,15 +264,13 @@ __device__ __forceinline__ void render_quadrant_1(const FwdArgs& A, const int ti
             if (lane == 0) ck_start[(size_t)(tile * 4 + q) * (size_t)chunks + nck] = kbase + (uint32_t)jc;
             run(jc, cnt);
         }
-        {
-            // the last blended entry of the batch, as a 1-based compacted index (48-byte entries: x / 48 = x * 43691 >> 21
-            // for x < 2^15)
-            const uint32_t ke = mark_e != 0xFFFFFFFFu ? kbase + (((mark_e - sp0) * 43691u) >> 21) + 1u : 0u;
-            const uint32_t ko = mark_o != 0xFFFFFFFFu ? kbase + (((mark_o - sp0) * 43691u) >> 21) : 0u;
-            last_k = max(last_k, max(ke, ko));
+        // the last blended entry of the batch, 1-based (0: none), and with it the pixel's last contributor so far as a
+        // compacted index and as a position in the TILE's list (n_contrib: looked up once per batch)
+        const uint32_t jl = marks_last_entry(mark_e, mark_o, sp0);
+        if (jl) {
+            last_k = kbase + jl;
+            last = __float_as_uint(srec[(jl - 1u) * 3 + 2].w);
         }
-        // the last contributor's position in the TILE's list (n_contrib), looked up once per batch
-        if (last_k > kbase) last = __float_as_uint(srec[(last_k - 1u - kbase) * 3 + 2].w);
         live = __ballot(T > 0.f) != 0ull;  // every pixel of the quadrant frozen: stop
     }
     {

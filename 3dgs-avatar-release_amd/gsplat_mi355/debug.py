@@ -67,7 +67,9 @@ def forward_state(settings, means3D, opacities, shs=None, colors_precomp=None, s
         ) if P > 0 else {}
         b = dict(
             point_list=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, 0), 4 * D, np.uint32),
-        ) if D > 0 else dict(point_list=np.zeros(0, np.uint32))
+            # the quadrants' compacted lists: quadrant q of tile t at [4 ranges[t, 0] + q n_t, ... + qcount[t, q])
+            qlist=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, 1), 16 * D, np.uint32),
+        ) if D > 0 else dict(point_list=np.zeros(0, np.uint32), qlist=np.zeros(0, np.uint32))
         im = dict(
             ranges=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 0), 8 * gx * gy, np.uint32).reshape(-1, 2),
             n_contrib=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 1), 4 * W * H, np.uint32).reshape(H, W),

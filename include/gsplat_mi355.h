@@ -469,6 +469,8 @@ int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* t
  *           (x, y, conicA, conicB, conicC, opacity, r, g, b, first pair u32, rect_min u32 (x | y<<16), rect_size u32 (w | h<<16))
  *           3 clamped bitmask u32[P]   4 depth-sorted Gaussian index u32[P]   5 num_rendered u64[1]
  *  binning: 0 point_list u32[D] (tile after tile, (depth, index) order inside a tile; tile t owns ranges[t] of it)
+ *           1 qlist u32[4 D]: the quadrants' compacted lists as the forward recorded them; quadrant q of tile t (n_t list
+ *             entries) owns [4 ranges[t].x + q n_t, ... + n_t), filled up to image field 3's count (at least)
  *  image:   0 ranges u32[tiles,2]   1 n_contrib u32[H,W]   2 final_T f32[H,W]
  *           3 per-quadrant compacted count up to the last contributor u32[tiles,4]
  *           4 per-pixel last contributor in compacted coordinates u32[H,W]
