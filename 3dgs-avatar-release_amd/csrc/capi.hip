@@ -4,6 +4,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
+#include <chrono>
+#include <mutex>
+#include <vector>
 
 static thread_local int g_last_hip = 0;
 static thread_local const char* g_last_stage = "";
@@ -12,36 +15,55 @@ void gs_set_error(int hip_err, const char* stage) {
     g_last_stage = stage;
 }
 
-static std::atomic<int> g_tune[GS_TUNE_COUNT] = {};
-static bool g_tune_init = false;
-static void tune_defaults() {
-    if (g_tune_init) return;
-    g_tune_init = true;
-    g_tune[GS_TUNE_XCD_MAP].store(1);
-    g_tune[GS_TUNE_DEPTH_SORT].store(1);
-    g_tune[GS_TUNE_NT_STORES].store(1);
-    g_tune[GS_TUNE_BWD_CHUNKS].store(1);
-    g_tune[GS_TUNE_FWD4].store(1);
-    // (GSPLAT_FWD4=0|1|2: the forward of the tiles marked as long on small images -- one wave per quadrant, four waves x four
-    // entries per step, or a wave per chunk of the list (render_fwd.hip: render_chunk); the same as gs_tuning("fwd4", v), read once)
-    if (const char* e = getenv("GSPLAT_FWD4")) g_tune[GS_TUNE_FWD4].store(atoi(e));
-    g_tune[GS_TUNE_FWDC_CH].store((int)FWDC_CH_MIN);  // entries per chunk of the chunk-parallel forward (a power of two >= 64)
-    g_tune[GS_TUNE_FWDC_DIV].store((int)FWD4_TOTAL_DIV);  // ... of the tiles whose list is longer than (frame's pairs) / this (and than FWD4_MIN_LIST)
-    if (const char* e = getenv("GSPLAT_FWDC_DIV")) { const int v = atoi(e); if (v >= 1) g_tune[GS_TUNE_FWDC_DIV].store(v); }
-    if (const char* e = getenv("GSPLAT_FWDC_CH")) { const int v = atoi(e); if (v >= 64 && (v & (v - 1)) == 0) g_tune[GS_TUNE_FWDC_CH].store(v); }
-    g_tune[GS_TUNE_SHARED_QLIST].store(1);
-    g_tune[GS_TUNE_ONES_FAST].store(1);
-    g_tune[GS_TUNE_SMALL_TILES].store(BWD_CHUNK_MAX_TILES);
-    g_tune[GS_TUNE_BWD_ORDER].store(1);
-    g_tune[GS_TUNE_FWD_MARKS].store(1);
+// ---- tuning switches: the one table behind gs_tuning, the defaults and the environment overrides (what each switch
+// does is documented at gs_tuning in include/gsplat_mi355.h, name for name)
+struct TuneSwitch {
+    const char* name;
+    int key, def;
+    const char* env;   // read once, when the first switch is read; a value the rule rejects is ignored
+    bool (*ok)(int);   // null: every value is taken
+};
+static const TuneSwitch k_tune[GS_TUNE_COUNT] = {
+    {"xcd_map", GS_TUNE_XCD_MAP, 1, nullptr, nullptr},
+    {"depth_sort", GS_TUNE_DEPTH_SORT, 1, nullptr, nullptr},  // 1 bucket sort, 0 LSD radix
+    {"nt_stores", GS_TUNE_NT_STORES, 1, nullptr, nullptr},
+    {"bwd_chunks", GS_TUNE_BWD_CHUNKS, 1, nullptr, nullptr},  // flip between frames only
+    // GSPLAT_FWD4=0|1|2: the forward of the tiles marked as long on small images -- one wave per quadrant, four waves x four
+    // entries per step, or a wave per chunk of the list (render_fwd.hip: render_chunk)
+    {"fwd4", GS_TUNE_FWD4, 1, "GSPLAT_FWD4", nullptr},
+    {"small_tiles", GS_TUNE_SMALL_TILES, BWD_CHUNK_MAX_TILES, nullptr, nullptr},  // changes the image state's size
+    {"shared_qlist", GS_TUNE_SHARED_QLIST, 1, nullptr, nullptr},
+    {"ones_fast", GS_TUNE_ONES_FAST, 1, nullptr, nullptr},
+    {"bwd_order", GS_TUNE_BWD_ORDER, 1, nullptr, nullptr},  // 0: the backward walks the tiles in the forward's launch order (A/B: + 12 us at config 3)
+    {"fwd_marks", GS_TUNE_FWD_MARKS, 1, nullptr, nullptr},  // 0: the backward sets its row marks itself (A/B)
+    // entries per chunk of the chunk-parallel forward (a power of two >= 64) ...
+    {"fwdc_ch", GS_TUNE_FWDC_CH, (int)FWDC_CH_MIN, "GSPLAT_FWDC_CH", [](int v) { return v >= 64 && (v & (v - 1)) == 0; }},
+    // ... of the tiles whose list is longer than (frame's pairs) / this (and than FWD4_MIN_LIST)
+    {"fwdc_div", GS_TUNE_FWDC_DIV, (int)FWD4_TOTAL_DIV, "GSPLAT_FWDC_DIV", [](int v) { return v >= 1; }},
+};
+struct TuneState {
+    std::atomic<int> v[GS_TUNE_COUNT];
+    TuneState() {
+        for (const TuneSwitch& t : k_tune) {
+            int value = t.def;
+            if (const char* e = t.env ? getenv(t.env) : nullptr) {
+                const int x = atoi(e);
+                if (!t.ok || t.ok(x)) value = x;
+            }
+            v[t.key].store(value);
+        }
+    }
+};
+// (a function-local static: initialised once however many threads ask first -- the forward's and autograd's backward thread do)
+static TuneState& tune_state() {
+    static TuneState st;
+    return st;
 }
 int gs_tune_get(int key) {
-    tune_defaults();
-    return (key >= 0 && key < GS_TUNE_COUNT) ? g_tune[key].load(std::memory_order_relaxed) : 0;
+    return (key >= 0 && key < GS_TUNE_COUNT) ? tune_state().v[key].load(std::memory_order_relaxed) : 0;
 }
 
 // ---- per-stage event timing -------------------------------------------------------------------
-#include <vector>
 struct ProfRec { const char* name; hipEvent_t a, b; };
 struct ProfState {
     bool on = false;
@@ -58,9 +80,6 @@ struct ProfState {
     }
 };
 // process-wide (autograd runs the backward on its own host thread), guarded by a mutex
-#include <mutex>
-#include <chrono>
-#include <atomic>
 static ProfState g_prof;
 static std::mutex g_prof_mu;
 static bool profiling_on() { return g_prof.on; }
@@ -169,6 +188,64 @@ __global__ __launch_bounds__(64) void xcc_probe_kernel(uint32_t* __restrict__ ou
     if (threadIdx.x == 0) out[blockIdx.x] = xcc_id();
 }
 
+// ---- what the frame path's entry points share -----------------------------------------------------------------
+// What every such entry point does first, in the order each of them has always done it: the common validation of `a`;
+// the null / range checks on the states (GS_E_BAD_ARG); the entry point's own argument checks (`own`: a callable that
+// answers a status); then the three carves -- views of const members where the state pointer is to const -- against the
+// sizes the caller passed (GS_E_WORKSPACE).  Nothing is enqueued.  (A call without a binning state: binning = (void*)0,
+// D = 0.  A frame without pairs has no binning view either: null members.)
+template <class Void, class VoidBin, class G, class B, class I, class Own>
+static int frame_states(const GsFwdArgs* a, Void* geom, size_t geom_bytes, VoidBin* binning, size_t binning_bytes, Void* img,
+                        size_t img_bytes, int64_t D, G* g, B* b, I* im, Own own) {
+    int rc = validate(a);
+    if (rc != GS_OK) return rc;
+    if (!geom || !img || D < 0 || (D > 0 && !binning)) return GS_E_BAD_ARG;
+    if ((rc = own()) != GS_OK) return rc;
+    *g = geom_state(geom, a->P);
+    *im = img_state(img, a->W, a->H, a->long_lists);
+    *b = bin_state(D > 0 ? binning : nullptr, D);
+    if (geom_bytes < g->total || img_bytes < im->total || (D > 0 && binning_bytes < b->total)) return GS_E_WORKSPACE;
+    return GS_OK;
+}
+
+// QuadLists serves the forward, which writes through it, and the backward, which only reads (launch_render_backward);
+// its members are not const, so a read-only image state is handed over like this
+template <class T> static T* writable(T* p) { return p; }
+template <class T> static T* writable(const T* p) { return const_cast<T*>(p); }
+// The members of QuadLists every render sets the same way, forward or backward, first or second image (four_waves is
+// the forward's; the backward does not look at it)
+template <bool RO>
+static QuadLists quad_lists(const ImgViewT<RO>& im, const BinView& b, int long_lists) {
+    QuadLists ql;
+    ql.qlist = b.qlist;
+    ql.ncon_c = writable(im.ncon_c);
+    ql.qcount = writable(im.qcount);
+    ql.chunks = gs_tune_get(GS_TUNE_BWD_CHUNKS) ? im.bwd_chunks : 1;
+    ql.four_waves = forward_small_image(im.ntiles, long_lists) ? 1 : 0;
+    ql.ckpt = ql.chunks > 1 ? writable(im.ckpt) : nullptr;
+    ql.ck_start = ql.chunks > 1 ? writable(im.ck_start) : nullptr;
+    return ql;
+}
+// ... and those of the chunk-parallel forward (render_fwd.hip: render_chunk): the work list of `list` -- this image
+// state's own, or for a second render the first render's -- and the hand-off words and records of `own`
+template <bool RO>
+static void quad_lists_chunked(QuadLists& ql, const ImgView& own, const ImgViewT<RO>& list) {
+    ql.chunked = 1;
+    ql.cw_hdr = list.cw_hdr;
+    ql.cw_units = list.cw_units;
+    ql.cw_items = list.cw_items;
+    ql.cw_q = own.cw_q;
+    ql.cw_flag = own.cw_flag;
+    ql.cw_done = own.cw_done;
+    ql.cw_rec = own.cw_rec;
+}
+static int sync_if_debug(const GsFwdArgs* a, const char* stage, hipStream_t s) {
+    if (!a->debug) return GS_OK;
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { gs_set_error((int)e, stage); return GS_E_HIP; }
+    return GS_OK;
+}
+
 extern "C" {
 
 int gs_xcc_probe(uint32_t* xcc, int32_t n_blocks, void* stream) {
@@ -221,65 +298,48 @@ int gs_backward_scratch_bytes(int64_t D, int32_t P, int32_t W, int32_t H, size_t
 // `poll`: a pinned host word the scan kernel writes the count into directly (gs_forward spins on it)
 static int forward_phase1(const GsFwdArgs* a, void* geom, size_t geom_bytes, void* img, size_t img_bytes, int32_t* radii,
                           int64_t* count_host_pinned, unsigned long long* poll, void* stream) {
-    int rc = validate(a);
+    GeomView g;
+    BinView none;
+    ImgView im;
+    int rc = frame_states(a, geom, geom_bytes, (void*)nullptr, 0, img, img_bytes, 0, &g, &none, &im,
+                          [&]() -> int { return (a->P > 0 && !radii) ? GS_E_BAD_ARG : GS_OK; });
     if (rc != GS_OK) return rc;
-    if (!geom || !img || (a->P > 0 && !radii)) return GS_E_BAD_ARG;
-    const GeomLayout L = geom_layout(a->P);
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    if (geom_bytes < L.total || img_bytes < I.total) return GS_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* g = (char*)geom;
-    unsigned long long* count = (unsigned long long*)(g + L.count);
     if (a->P == 0) {
-        rc = gs_zero_async(count, 24, "count.zero", s);
+        rc = gs_zero_async(g.count, COUNT_ZERO_BYTES, "count.zero", s);
         if (rc != GS_OK) return rc;
     } else {
-        uint32_t* k0 = (uint32_t*)(g + L.key0);
-        uint32_t* k1 = (uint32_t*)(g + L.key1);
-        uint32_t* v0 = (uint32_t*)(g + L.val0);
-        uint32_t* v1 = (uint32_t*)(g + L.val1);
         ZeroJob zt;  // the depth sort's digit totals, cleared by the preprocess kernel
-        sort_totals_region((uint32_t*)(g + L.hist), a->P, 32, &zt.ptr, &zt.words);
+        sort_totals_region(g.hist, a->P, 32, &zt.ptr, &zt.words);
         // ... and the image state's per-tile pair totals, which phase 2's counting pass adds into
-        const ZeroJob zi{(uint32_t*)((char*)img + I.tile_tot), (int)(I.tile_zero_bytes / 4)};
+        const ZeroJob zi{im.tile_tot, (int)(im.tile_zero_bytes / 4)};
         { StageScope sc_("preprocess", s);
-        rc = launch_preprocess(*a, (float*)(g + L.rec), (float*)(g + L.depths), (uint32_t*)(g + L.tiles),
-                               (uint32_t*)(g + L.clamped), k0, v0, radii, (uint32_t*)(g + L.wsum), (uint32_t*)(g + L.wkmin),
-                               (uint32_t*)(g + L.wkmax), zt, zi, s); }
+        rc = launch_preprocess(*a, g.rec, g.depths, g.tiles, g.clamped, g.key0, g.val0, radii, g.wsum, g.wkmin, g.wkmax, zt, zi, s); }
         if (rc != GS_OK) return rc;
         // pair numbering (Gaussian-major, index order) and the pair count need nothing of the depth sort, so the count is
         // on its way to the host while the sort runs; (depth key, index) order: ties keep ascending Gaussian index (the
-        // reference's tie order); the ranking ends in v0 and, with what binning needs of every Gaussian, in the rank list
+        // reference's tie order); the ranking ends in val0 and, with what binning needs of every Gaussian, in the rank list
         if (gs_tune_get(GS_TUNE_DEPTH_SORT)) {
             StageScope sc_("depth_sort", s);  // the numbering rides in its first launch, the rank list in its last ones
-            const DepthSortState st{(unsigned long long*)(g + L.ds_tmp), (unsigned long long*)(g + L.ds_tmp2),
-                                    (uint32_t*)(g + L.ds_cnt), (uint32_t*)(g + L.ds_pre),
-                                    (uint32_t*)(g + L.ds_tot),
-                                    (uint32_t*)(g + L.ds_loc), (uint32_t*)(g + L.ds_grp), (uint32_t*)(g + L.ds_range), L.ds_nb,
-                                    L.ds_blocks};
-            const PairNumbering pn{(const uint32_t*)(g + L.tiles), (const uint32_t*)(g + L.wsum), (float*)(g + L.rec), count, poll,
-                                   (uint32_t*)(g + L.chunk_pairs), (a->P + 255) / 256};
-            const RankOut ro{(const float*)(g + L.rec), (const uint32_t*)(g + L.tiles), v0, (uint4*)(g + L.ranklist),
-                             (uint32_t*)(g + L.chunk_pairs)};
-            rc = launch_depth_sort(k0, (const uint32_t*)(g + L.wkmin), (const uint32_t*)(g + L.wkmax), L.nwaves, a->P, st, pn, ro,
-                                   a->debug, s);
+            const DepthSortState ds{g.ds_tmp, g.ds_tmp2, g.ds_cnt, g.ds_pre, g.ds_tot, g.ds_loc, g.ds_grp, g.ds_range, g.ds_nb, g.ds_blocks};
+            const PairNumbering pn{g.tiles, g.wsum, g.rec, g.count, poll, g.chunk_pairs, (a->P + 255) / 256};
+            const RankOut ro{g.rec, g.tiles, g.val0, g.ranklist, g.chunk_pairs};
+            rc = launch_depth_sort(g.key0, g.wkmin, g.wkmax, g.nwaves, a->P, ds, pn, ro, a->debug, s);
             if (rc != GS_OK) return rc;
-        } else {  // the LSD radix sort (gs_tuning "depth_sort" = 0): 4 passes, ends in (k0, v0)
+        } else {  // the LSD radix sort (gs_tuning "depth_sort" = 0): 4 passes, ends in (key0, val0)
             { StageScope sc_("pair_scan", s);
-            rc = launch_first_pair((const uint32_t*)(g + L.tiles), (const uint32_t*)(g + L.wsum), (float*)(g + L.rec), count, poll,
-                                   a->P, a->debug, s); }
+            rc = launch_first_pair(g.tiles, g.wsum, g.rec, g.count, poll, a->P, a->debug, s); }
             if (rc != GS_OK) return rc;
             { StageScope sc_("depth_sort", s);
-            rc = launch_sort_pairs(k0, v0, k1, v1, (uint32_t*)(g + L.hist), a->P, 32, true, a->debug, s); }
+            rc = launch_sort_pairs(g.key0, g.val0, g.key1, g.val1, g.hist, a->P, 32, true, a->debug, s); }
             if (rc != GS_OK) return rc;
             { StageScope sc_("rank_list", s);
-            rc = launch_rank_list(v0, (const float*)(g + L.rec), (const uint32_t*)(g + L.tiles), (uint4*)(g + L.ranklist),
-                                  (uint32_t*)(g + L.chunk_pairs), a->P, a->debug, s); }
+            rc = launch_rank_list(g.val0, g.rec, g.tiles, g.ranklist, g.chunk_pairs, a->P, a->debug, s); }
             if (rc != GS_OK) return rc;
         }
     }
     if (count_host_pinned && (!poll || a->P == 0)) {
-        hipError_t e = hipMemcpyAsync(count_host_pinned, count, 8, hipMemcpyDeviceToHost, s);
+        hipError_t e = hipMemcpyAsync(count_host_pinned, g.count, 8, hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) { gs_set_error((int)e, "count.copy"); return GS_E_HIP; }
     }
     return GS_OK;
@@ -297,90 +357,57 @@ int gs_forward_preprocess(const GsFwdArgs* a, void* geom, size_t geom_bytes, voi
 // `totals_zeroed`: phase 1 has just run on this image state (its preprocess kernel cleared the per-tile pair totals).
 static int forward_phase2(const GsFwdArgs* a, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes, void* img,
                           size_t img_bytes, int64_t cap, float* out_color, void* stream, bool totals_zeroed) {
-    if (!geom || !img || !out_color || cap < 0 || (cap > 0 && !binning)) return GS_E_BAD_ARG;
-    if (a->l1_target && !a->l1_loss) return GS_E_BAD_ARG;  // the fused L1 loss needs somewhere to put its value
-    if (cap > GS_MAX_PAIRS) return GS_E_TOO_LARGE;
-    const GeomLayout L = geom_layout(a->P);
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    const BinLayout B = bin_layout(cap);
-    if (geom_bytes < L.total || img_bytes < I.total || (cap > 0 && binning_bytes < B.total)) return GS_E_WORKSPACE;
+    GeomView g;
+    BinView b;
+    ImgView im;
+    int rc = frame_states(a, geom, geom_bytes, binning, binning_bytes, img, img_bytes, cap, &g, &b, &im, [&]() -> int {
+        if (!out_color) return GS_E_BAD_ARG;
+        if (a->l1_target && !a->l1_loss) return GS_E_BAD_ARG;  // the fused L1 loss needs somewhere to put its value
+        return cap > GS_MAX_PAIRS ? GS_E_TOO_LARGE : GS_OK;
+    });
+    if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* g = (char*)geom;
-    char* b = (char*)binning;
-    char* im = (char*)img;
-    const int ntiles = I.gx * I.gy;
-    uint32_t* ranges = (uint32_t*)(im + I.ranges);
-    const uint32_t* point_list = nullptr;
-    const unsigned long long* count_dev = (const unsigned long long*)(g + L.count);
-    const PairCount pc{count_dev, (uint32_t)cap};
-    const bool chunked = forward_chunked(ntiles, a->long_lists);  // the marked tiles chunk-parallel (render_fwd.hip: render_chunk)
-    int rc;
+    const PairCount pc{g.count + COUNT_PAIRS, (uint32_t)cap};
+    // the marked tiles chunk-parallel (render_fwd.hip: render_chunk): the image state has the cw_* fields exactly then
+    const bool chunked = forward_chunked(im.ntiles, a->long_lists);
     if (a->P > 0) {
-        point_list = cap > 0 ? (const uint32_t*)(b + B.point_list) : nullptr;
-        rc = launch_tile_lists((const uint4*)(g + L.ranklist), (const uint32_t*)(g + L.chunk_pairs), (uint32_t*)(g + L.seg_start),
-                               a->P, I.gx, I.gy,
-                               TileCounts{(uint32_t*)(im + I.seg_cnt), (uint32_t*)(im + I.tile_tot), I.tile_zero_bytes,
-                                          chunked ? (uint32_t*)(im + I.cw_q) + 8 * FWDC_MAX_UNITS * 4 : nullptr},
-                               ranges, (uint32_t*)(im + I.order),
-                               cap > 0 ? (uint32_t*)(b + B.point_list) : nullptr, pc,
-                               LongLists{chunked ? 2 : (forward_small_image(ntiles, a->long_lists) ? 1 : 0), (long long*)a->frame_stats,
-                                         chunked ? (uint32_t*)(im + I.cw_hdr) : nullptr, chunked ? (uint2*)(im + I.cw_units) : nullptr,
-                                         (uint32_t)gs_tune_get(GS_TUNE_FWDC_CH), chunked ? (uint32_t*)(im + I.cw_items) : nullptr,
-                                         chunked ? (const uint32_t*)(im + I.cw_q) + 8 * FWDC_MAX_UNITS * 4 : nullptr,
+        rc = launch_tile_lists(g.ranklist, g.chunk_pairs, g.seg_start, a->P, im.gx, im.gy,
+                               TileCounts{im.seg_cnt, im.tile_tot, im.tile_zero_bytes, im.cw_xcc_mask}, im.ranges, im.order,
+                               b.point_list, pc,
+                               LongLists{chunked ? 2 : (forward_small_image(im.ntiles, a->long_lists) ? 1 : 0), (long long*)a->frame_stats,
+                                         im.cw_hdr, im.cw_units, (uint32_t)gs_tune_get(GS_TUNE_FWDC_CH), im.cw_items, im.cw_xcc_mask,
                                          chunked ? (uint32_t)gs_tune_get(GS_TUNE_FWDC_DIV) : (uint32_t)FWD4_TOTAL_DIV},
                                totals_zeroed, a->debug, s);
         if (rc != GS_OK) return rc;
     } else {
-        rc = gs_zero_async(ranges, (size_t)ntiles * 8, "ranges.zero", s);
+        rc = gs_zero_async(im.ranges, (size_t)im.ntiles * 8, "ranges.zero", s);
         if (rc != GS_OK) return rc;
         StageScope sc_("ranges_order", s);
-        rc = launch_tile_order(ranges, nullptr, 0, ntiles, (uint32_t*)(im + I.order), pc, FillJob{nullptr, 0},
-                               LongLists{0, nullptr, chunked ? (uint32_t*)(im + I.cw_hdr) : nullptr, nullptr}, a->debug, s);
+        rc = launch_tile_order(im.ranges, nullptr, 0, im.ntiles, im.order, pc, FillJob{nullptr, 0},
+                               LongLists{0, nullptr, im.cw_hdr, nullptr}, a->debug, s);
         if (rc != GS_OK) return rc;
     }
-    QuadLists ql;
-    ql.qlist = cap > 0 ? (uint32_t*)(b + B.qlist) : nullptr;
-    ql.ncon_c = (uint32_t*)(im + I.ncon_c);
-    ql.qcount = (uint32_t*)(im + I.tile_nmax);
-    ql.chunks = gs_tune_get(GS_TUNE_BWD_CHUNKS) ? I.bwd_chunks : 1;
-    ql.four_waves = forward_small_image(I.gx * I.gy, a->long_lists) ? 1 : 0;
-    if (chunked) {
-        ql.chunked = 1;
-        ql.cw_hdr = (const uint32_t*)(im + I.cw_hdr);
-        ql.cw_units = (const uint2*)(im + I.cw_units);
-        ql.cw_items = (const uint32_t*)(im + I.cw_items);
-        ql.cw_q = (uint32_t*)(im + I.cw_q);
-        ql.cw_flag = (uint32_t*)(im + I.cw_flag);
-        ql.cw_done = (uint32_t*)(im + I.cw_done);
-        ql.cw_rec = (float*)(im + I.cw_rec);
-    }
-    ql.ckpt = ql.chunks > 1 ? (float4*)(im + I.ckpt) : nullptr;
-    ql.ck_start = ql.chunks > 1 ? (uint32_t*)(im + I.ck_start) : nullptr;
+    QuadLists ql = quad_lists(im, b, a->long_lists);
+    if (chunked) quad_lists_chunked(ql, im, im);
     if (cap > 0) {  // the backward's row marks, set on the side by the render launch (BinLayout::marks) -- or declared unset
         // (not for a frame no backward can follow -- GsFwdArgs.forward_only: a frame rendered under no_grad)
-        ql.marks = (gs_tune_get(GS_TUNE_FWD_MARKS) && !a->forward_only) ? (uint4*)(b + B.marks) : nullptr;
+        ql.marks = (gs_tune_get(GS_TUNE_FWD_MARKS) && !a->forward_only) ? b.marks : nullptr;
         ql.mark_quads = (size_t)cap;
-        ql.marks_flag = (uint32_t*)(b + B.marks_flag);
+        ql.marks_flag = b.marks_flag;
     }
     ql.l1_target = a->l1_target;  // the fused L1 loss rides in the render launch (+ its one-workgroup final sum)
-    ql.l1_part = (float*)(im + I.l1_part);
+    ql.l1_part = im.l1_part;
     ql.l1_loss = a->l1_loss;
     { StageScope sc_("render_fwd", s);
-    rc = launch_render_forward((const float*)(g + L.rec), point_list, ranges, (const uint32_t*)(im + I.order), a->bg,
-                               a->W, a->H, out_color, (float*)(im + I.final_T), (uint32_t*)(im + I.n_contrib), ql, s); }
+    rc = launch_render_forward(g.rec, a->P > 0 ? b.point_list : nullptr, im.ranges, im.order, a->bg, a->W, a->H, out_color,
+                               im.final_T, im.n_contrib, ql, s); }
     if (rc != GS_OK) return rc;
-    if (a->debug) {
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gs_set_error((int)e, "render_forward"); return GS_E_HIP; }
-    }
-    return GS_OK;
+    return sync_if_debug(a, "render_forward", s);
 }
 
 int gs_forward_render(const GsFwdArgs* a, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes,
                       void* img, size_t img_bytes, int64_t D, float* out_color, void* stream) {
     GS_CAPTURE_OK_IF(stream, a && !a->debug && a->frame_stats == nullptr);
-    int rc = validate(a);
-    if (rc != GS_OK) return rc;
     return forward_phase2(a, geom, geom_bytes, binning, binning_bytes, img, img_bytes, D, out_color, stream, false);
 }
 
@@ -425,7 +452,7 @@ int gs_forward(const GsFwdArgs* a, void* geom, size_t geom_bytes, void* binning,
             // use the copy + synchronise form from now on
             poll_works.store(false, std::memory_order_relaxed);
             int64_t c = 0;
-            e = hipMemcpy(&c, (const char*)geom + geom_layout(a->P).count, 8, hipMemcpyDeviceToHost);
+            e = hipMemcpy(&c, geom_state(geom, a->P).count + COUNT_PAIRS, 8, hipMemcpyDeviceToHost);
             if (e != hipSuccess) { gs_set_error((int)e, "count.copy"); return GS_E_HIP; }
             *word = c;
         }
@@ -441,93 +468,60 @@ int gs_forward_shared(const GsFwdArgs* a, const void* geom_src, const void* img_
                       void* binning, size_t binning_bytes, void* img, size_t img_bytes, int64_t D, float* out_color,
                       void* stream) {
     GS_CAPTURE_OK_IF(stream, a && !a->debug && a->P > 0);
-    int rc = validate(a);
+    GeomView g;  // THIS render's states, written ...
+    BinView b;
+    ImgView im;
+    int rc = frame_states(a, geom, geom_bytes, binning, binning_bytes, img, img_bytes, D, &g, &b, &im,
+                          [&]() -> int { return (!geom_src || !img_src || !out_color) ? GS_E_BAD_ARG : GS_OK; });
     if (rc != GS_OK) return rc;
-    if (!geom_src || !img_src || !geom || !img || !out_color || D < 0 || (D > 0 && !binning)) return GS_E_BAD_ARG;
-    const GeomLayout L = geom_layout(a->P);
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    const BinLayout B = bin_layout(D);
-    if (geom_bytes < L.total || img_bytes < I.total || (D > 0 && binning_bytes < B.total)) return GS_E_WORKSPACE;
+    // ... and the FIRST render's, read (the caller passes the SAME long_lists as to the first render, so that both image
+    // states have the same layout)
+    const GeomViewRO first_g = geom_state(geom_src, a->P);
+    const ImgViewRO first_im = img_state(img_src, a->W, a->H, a->long_lists);
     hipStream_t s = (hipStream_t)stream;
-    const char* gs = (const char*)geom_src;
-    const char* is = (const char*)img_src;
-    char* g = (char*)geom;
-    char* b = (char*)binning;
-    char* im = (char*)img;
-    const int ntiles = I.gx * I.gy;
-    const bool chunked = forward_chunked(ntiles, a->long_lists);
+    const bool chunked = forward_chunked(im.ntiles, a->long_lists);  // (im and first_im have the cw_* fields exactly then)
+    QuadLists ql = quad_lists(im, b, a->long_lists);  // (qlist: read, not rewritten -- the recorded quadrant lists are what is walked)
     unsigned long long* not_ones = nullptr;
     if (a->P > 0) {
         StageScope sc_("recolor", s);
-        // (the first render's geom state carries the "not all ones" word, zero since that render; the caller passes the
-        // SAME long_lists as to the first render, so that both image states have the same layout)
-        not_ones = (gs_tune_get(GS_TUNE_ONES_FAST) && gs_tune_get(GS_TUNE_SHARED_QLIST) && a->colors_precomp && D > 0)
-                       ? (unsigned long long*)(const_cast<char*>(gs) + L.count) + 2 : nullptr;
+        // (the first render's geom state carries the "not all ones" word, zero since that render)
+        if (gs_tune_get(GS_TUNE_ONES_FAST) && gs_tune_get(GS_TUNE_SHARED_QLIST) && a->colors_precomp && D > 0)
+            not_ones = not_ones_word(first_g);
         // ... and, when the colours may turn out to be all ones, the launch's other workgroups write the image that is
         // right in that case (1 - T of the first render, with its records): the render launch below then leaves at once
-        const int chunks_ = gs_tune_get(GS_TUNE_BWD_CHUNKS) ? I.bwd_chunks : 1;
-        const SecondOnes so{(const float*)(is + I.final_T), (const uint32_t*)(is + I.n_contrib), (const uint32_t*)(is + I.ncon_c),
-                            (const uint32_t*)(is + I.tile_nmax), (const float4*)(is + I.ckpt), (const uint32_t*)(is + I.ck_start),
-                            out_color, (float*)(im + I.final_T), (uint32_t*)(im + I.n_contrib), (uint32_t*)(im + I.ncon_c),
-                            (uint32_t*)(im + I.tile_nmax), chunks_ > 1 ? (float4*)(im + I.ckpt) : nullptr,
-                            chunks_ > 1 ? (uint32_t*)(im + I.ck_start) : nullptr, a->bg, a->W, a->H, I.gx, ntiles,
-                            chunks_ > 1 ? chunks_ : 1};
-        rc = launch_recolor(*a, (const float*)(gs + L.rec), (const uint32_t*)(gs + L.tiles), (float*)(g + L.rec),
-                            (uint32_t*)(g + L.tiles), (uint32_t*)(g + L.clamped), not_ones,
-                            CopyJob{(const uint32_t*)(is + I.ranges), (uint32_t*)(im + I.ranges), ntiles * 2},
-                            CopyJob{(const uint32_t*)(is + I.order), (uint32_t*)(im + I.order), ntiles},
-                            chunked ? ZeroJob{(uint32_t*)(im + I.cw_flag), (int)((I.cw_q + (size_t)8 * FWDC_MAX_UNITS * 4 * 4 + 64 - I.cw_flag) / 4)} : ZeroJob{nullptr, 0},
-                            not_ones ? &so : nullptr, s);
+        const SecondOnes so{first_im.final_T, first_im.n_contrib, first_im.ncon_c, first_im.qcount, first_im.ckpt, first_im.ck_start,
+                            out_color, im.final_T, im.n_contrib, im.ncon_c, im.qcount, ql.ckpt, ql.ck_start, a->bg, a->W, a->H,
+                            im.gx, im.ntiles, ql.chunks};
+        rc = launch_recolor(*a, first_g.rec, first_g.tiles, g.rec, g.tiles, g.clamped, not_ones,
+                            CopyJob{first_im.ranges, im.ranges, im.ntiles * 2}, CopyJob{first_im.order, im.order, im.ntiles},
+                            ZeroJob{im.cw_flag, im.cw_clear_words}, not_ones ? &so : nullptr, s);
         if (rc != GS_OK) return rc;
     } else {
         // (no Gaussians: no recolouring launch to ride in) the new image state's own copy of the tile ranges and launch order
-        hipError_t e = hipMemcpyAsync(im + I.ranges, is + I.ranges, (size_t)ntiles * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(im + I.order, is + I.order, (size_t)ntiles * 4, hipMemcpyDeviceToDevice, s);
+        hipError_t e = hipMemcpyAsync(im.ranges, first_im.ranges, (size_t)im.ntiles * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(im.order, first_im.order, (size_t)im.ntiles * 4, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) { gs_set_error((int)e, "shared.copy"); return GS_E_HIP; }
     }
-    hipError_t e = hipSuccess;
-    const uint32_t* point_list = D > 0 ? (const uint32_t*)(b + B.point_list) : nullptr;
-    QuadLists ql;
-    ql.qlist = D > 0 ? (uint32_t*)(b + B.qlist) : nullptr;  // read, not rewritten: the recorded quadrant lists are what is walked
-    ql.ncon_c = (uint32_t*)(im + I.ncon_c);
-    ql.qcount = (uint32_t*)(im + I.tile_nmax);
     if (gs_tune_get(GS_TUNE_SHARED_QLIST)) {
-        ql.src_qcount = (const uint32_t*)(is + I.tile_nmax);  // (the fields before the checkpoints sit at the same offsets
-        ql.src_n_contrib = (const uint32_t*)(is + I.n_contrib);  //  whatever long_lists the first render was given)
+        ql.src_qcount = first_im.qcount;        // (the fields before the checkpoints sit at the same offsets
+        ql.src_n_contrib = first_im.n_contrib;  //  whatever long_lists the first render was given)
         ql.not_ones = not_ones;
     }
-    ql.chunks = gs_tune_get(GS_TUNE_BWD_CHUNKS) ? I.bwd_chunks : 1;
-    ql.four_waves = forward_small_image(I.gx * I.gy, a->long_lists) ? 1 : 0;
     if (chunked && a->P > 0) {
         // the first render's work list (the copied launch order carries its marks); this state's own hand-off words
         // (cleared by the recolouring launch) and records; walking the recorded lists also the first render's records
-        ql.chunked = 1;
-        ql.cw_hdr = (const uint32_t*)(is + I.cw_hdr);
-        ql.cw_units = (const uint2*)(is + I.cw_units);
-        ql.cw_items = (const uint32_t*)(is + I.cw_items);
-        ql.cw_q = (uint32_t*)(im + I.cw_q);
-        ql.cw_flag = (uint32_t*)(im + I.cw_flag);
-        ql.cw_done = (uint32_t*)(im + I.cw_done);
-        ql.cw_rec = (float*)(im + I.cw_rec);
+        quad_lists_chunked(ql, im, first_im);
         if (ql.src_qcount) {
-            ql.src_cw_flag = (const uint32_t*)(is + I.cw_flag);
-            ql.src_cw_rec = (const float*)(is + I.cw_rec);
-            ql.src_final_T = (const float*)(is + I.final_T);
+            ql.src_cw_flag = first_im.cw_flag;
+            ql.src_cw_rec = first_im.cw_rec;
+            ql.src_final_T = first_im.final_T;
         }
     }
-    ql.ckpt = ql.chunks > 1 ? (float4*)(im + I.ckpt) : nullptr;
-    ql.ck_start = ql.chunks > 1 ? (uint32_t*)(im + I.ck_start) : nullptr;
-    ql.all_ones = (uint32_t*)(im + I.all_ones);  // (set by the render launch: 1 iff it left the speculative image alone)
+    ql.all_ones = im.all_ones;  // (set by the render launch: 1 iff it left the speculative image alone)
     { StageScope sc_("render_fwd", s);
-    rc = launch_render_forward((const float*)(g + L.rec), point_list, (const uint32_t*)(im + I.ranges),
-                               (const uint32_t*)(im + I.order), a->bg, a->W, a->H, out_color, (float*)(im + I.final_T),
-                               (uint32_t*)(im + I.n_contrib), ql, s); }
+    rc = launch_render_forward(g.rec, b.point_list, im.ranges, im.order, a->bg, a->W, a->H, out_color, im.final_T, im.n_contrib, ql, s); }
     if (rc != GS_OK) return rc;
-    if (a->debug) {
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gs_set_error((int)e, "render_forward"); return GS_E_HIP; }
-    }
-    return GS_OK;
+    return sync_if_debug(a, "render_forward", s);
 }
 
 int gs_opacity_image(const GsFwdArgs* a, const void* img, size_t img_bytes, float* opacity, void* stream) {
@@ -535,9 +529,9 @@ int gs_opacity_image(const GsFwdArgs* a, const void* img, size_t img_bytes, floa
     int rc = validate(a);
     if (rc != GS_OK) return rc;
     if (!img || !opacity) return GS_E_BAD_ARG;
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    if (img_bytes < I.total) return GS_E_WORKSPACE;
-    return launch_opacity_image((const float*)((const char*)img + I.final_T), a->bg, a->W, a->H, opacity, (hipStream_t)stream);
+    const ImgViewRO im = img_state(img, a->W, a->H, a->long_lists);
+    if (img_bytes < im.total) return GS_E_WORKSPACE;
+    return launch_opacity_image(im.final_T, a->bg, a->W, a->H, opacity, (hipStream_t)stream);
 }
 
 static int backward_impl(const GsFwdArgs* a, const int32_t* radii, const void* geom, size_t geom_bytes, void* binning,
@@ -545,71 +539,53 @@ static int backward_impl(const GsFwdArgs* a, const int32_t* radii, const void* g
                          const float* dL_dpix, const float* dL_dopacity_img, void* scratch, size_t scratch_bytes,
                          const GsGrads* gr, void* stream, const GsSecondImage* second = nullptr) {
     GS_CAPTURE_OK_IF(stream, a && !a->debug);
-    int rc = validate(a);
+    GeomViewRO g;
+    BinView b;
+    ImgViewRO im;
+    int rc = frame_states(a, geom, geom_bytes, binning, binning_bytes, img, img_bytes, D, &g, &b, &im, [&]() -> int {
+        if (!out_color || (!dL_dpix && !a->l1_target) || !gr || (a->P > 0 && !scratch)) return GS_E_BAD_ARG;
+        if (a->P > 0 && (!radii || !gr->dL_dmeans3D || !gr->dL_dmeans2D || !gr->dL_dcolors || !gr->dL_dopacity || !gr->dL_dcov3D))
+            return GS_E_BAD_ARG;
+        if (a->P > 0 && a->shs && !gr->dL_dsh) return GS_E_BAD_ARG;
+        if (a->P > 0 && a->scales && (!gr->dL_dscales || !gr->dL_drotations)) return GS_E_BAD_ARG;
+        if (gr->dL_drotations && ((uintptr_t)gr->dL_drotations & 15u)) return GS_E_BAD_ARG;  // written as float4
+        return GS_OK;
+    });
     if (rc != GS_OK) return rc;
-    if (!geom || !img || !out_color || (!dL_dpix && !a->l1_target) || !gr || D < 0 || (D > 0 && !binning) || (a->P > 0 && !scratch))
-        return GS_E_BAD_ARG;
-    if (a->P > 0 && (!radii || !gr->dL_dmeans3D || !gr->dL_dmeans2D || !gr->dL_dcolors || !gr->dL_dopacity || !gr->dL_dcov3D))
-        return GS_E_BAD_ARG;
-    if (a->P > 0 && a->shs && !gr->dL_dsh) return GS_E_BAD_ARG;
-    if (a->P > 0 && a->scales && (!gr->dL_dscales || !gr->dL_drotations)) return GS_E_BAD_ARG;
-    if (gr->dL_drotations && ((uintptr_t)gr->dL_drotations & 15u)) return GS_E_BAD_ARG;  // written as float4
-    const GeomLayout L = geom_layout(a->P);
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    const BinLayout B = bin_layout(D);
-    size_t need = 0;
-    gs_backward_scratch_bytes(D, a->P, a->W, a->H, &need);
-    if (geom_bytes < L.total || img_bytes < I.total || (D > 0 && binning_bytes < B.total) || (a->P > 0 && scratch_bytes < need))
-        return GS_E_WORKSPACE;
+    if (a->P > 0 && scratch_bytes < scratch_total_bytes(D, a->P, im.ntiles)) return GS_E_WORKSPACE;
     if (a->P == 0) return GS_OK;
     hipStream_t s = (hipStream_t)stream;
-    const char* g = (const char*)geom;
-    char* b = (char*)binning;
-    const char* im = (const char*)img;
+    float* const sums = (float*)((char*)scratch + scratch_rows_bytes(D));
     if (D > 0) {
-        QuadLists ql;
-        ql.qlist = (uint32_t*)(b + B.qlist);
-        ql.ncon_c = (uint32_t*)(im + I.ncon_c);
-        ql.qcount = (uint32_t*)(im + I.tile_nmax);
-        ql.chunks = gs_tune_get(GS_TUNE_BWD_CHUNKS) ? I.bwd_chunks : 1;
-        ql.ckpt = ql.chunks > 1 ? (float4*)(im + I.ckpt) : nullptr;
-        ql.ck_start = ql.chunks > 1 ? (uint32_t*)(im + I.ck_start) : nullptr;
-        // the row marks: in the binning state, where the forward has set every word to ROW_UNWRITTEN beside its render
-        // kernel; if a backward has run on this state since (marks_flag), the tile-order launch's other workgroups do it
-        uint32_t* q8 = (uint32_t*)(b + B.marks);
-        uint32_t* marks_flag = (uint32_t*)(b + B.marks_flag);
-        uint32_t* order_b = (uint32_t*)((char*)scratch + scratch_rows_bytes(D) + scratch_sums_bytes(a->P));
-        const bool own_order = gs_tune_get(GS_TUNE_BWD_ORDER) != 0;
-        { StageScope sc_("tile_order", s);
-        rc = launch_tile_order((const uint32_t*)(im + I.ranges), ql.qcount, own_order ? 1 : -1, I.gx * I.gy, order_b, PairCount{nullptr, 0},
-                               FillJob{reinterpret_cast<uint4*>(q8), (size_t)D, gs_tune_get(GS_TUNE_NT_STORES) & 1, marks_flag},
-                               LongLists{0, nullptr}, a->debug, s); }
-        if (rc != GS_OK) return rc;
-        if (!own_order) order_b = (uint32_t*)(const_cast<char*>(im) + I.order);
+        const QuadLists ql = quad_lists(im, b, a->long_lists);
         SecondImage si{nullptr, nullptr, nullptr, nullptr, nullptr};
         if (second) {
             // the second render's own image state: its checkpoints (same chunk boundaries: same geometry, same rule)
-            const ImgLayout I2 = img_layout(a->W, a->H, second->long_lists);
-            if (second->img_bytes < I2.total || I2.bwd_chunks != I.bwd_chunks) return GS_E_BAD_ARG;
-            si = SecondImage{second->colors, second->out_color, second->dL_dpix,
-                             ql.chunks > 1 ? (const float4*)((const char*)second->img + I2.ckpt) : nullptr,
-                             (const uint32_t*)((const char*)second->img + I2.all_ones)};
+            const ImgViewRO im2 = img_state(second->img, a->W, a->H, second->long_lists);
+            if (second->img_bytes < im2.total || im2.bwd_chunks != im.bwd_chunks) return GS_E_BAD_ARG;
+            si = SecondImage{second->colors, second->out_color, second->dL_dpix, ql.chunks > 1 ? im2.ckpt : nullptr, im2.all_ones};
         }
-        { StageScope sc_("render_bwd", s);
-        rc = launch_render_backward((const float*)(g + L.rec), (const uint32_t*)(im + I.ranges), order_b, a->W, a->H, ql,
-                                    out_color, dL_dpix, dL_dopacity_img, (const float*)(im + I.final_T), a->bg, (float*)scratch, q8,
-                                    second ? &si : nullptr, L1Grad{a->l1_target, a->l1_grad}, s); }
+        // the row marks: in the binning state, where the forward has set every word to ROW_UNWRITTEN beside its render
+        // kernel; if a backward has run on this state since (marks_flag), the tile-order launch's other workgroups do it
+        uint32_t* const q8 = reinterpret_cast<uint32_t*>(b.marks);
+        uint32_t* const own_order = (uint32_t*)((char*)sums + scratch_sums_bytes(a->P));
+        const bool order_here = gs_tune_get(GS_TUNE_BWD_ORDER) != 0;
+        { StageScope sc_("tile_order", s);
+        rc = launch_tile_order(im.ranges, ql.qcount, order_here ? 1 : -1, im.ntiles, own_order, PairCount{nullptr, 0},
+                               FillJob{b.marks, (size_t)D, gs_tune_get(GS_TUNE_NT_STORES) & 1, b.marks_flag},
+                               LongLists{0, nullptr}, a->debug, s); }
         if (rc != GS_OK) return rc;
-        if (a->debug) {
-            hipError_t e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { gs_set_error((int)e, "render_backward"); return GS_E_HIP; }
-        }
+        { StageScope sc_("render_bwd", s);
+        rc = launch_render_backward(g.rec, im.ranges, order_here ? own_order : im.order, a->W, a->H, ql, out_color, dL_dpix,
+                                    dL_dopacity_img, im.final_T, a->bg, (float*)scratch, q8, second ? &si : nullptr,
+                                    L1Grad{a->l1_target, a->l1_grad}, s); }
+        if (rc != GS_OK) return rc;
+        rc = sync_if_debug(a, "render_backward", s);
+        if (rc != GS_OK) return rc;
     }
     StageScope sc_("gaussian_bwd", s);
-    return launch_gaussian_backward(*a, radii, (const float*)(g + L.rec), (const uint32_t*)(g + L.tiles),
-                                    (const uint32_t*)(g + L.clamped), D > 0 ? (const uint32_t*)(b + B.marks) : nullptr,
-                                    (const float*)scratch, (float*)((char*)scratch + scratch_rows_bytes(D)),
-                                    D > 0 ? (uint32_t*)(b + B.marks_flag) : nullptr, *gr, s);
+    return launch_gaussian_backward(*a, radii, g.rec, g.tiles, g.clamped, reinterpret_cast<const uint32_t*>(b.marks),
+                                    (const float*)scratch, sums, b.marks_flag, *gr, s);
 }
 
 int gs_backward(const GsFwdArgs* a, const int32_t* radii, const void* geom, size_t geom_bytes, void* binning,
@@ -959,66 +935,60 @@ int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, i
 int gs_pair_stats(const GsFwdArgs* a, const void* geom, size_t geom_bytes, const void* binning, size_t binning_bytes, const void* img,
                   size_t img_bytes, int64_t D, uint64_t* counts, void* stream) {
     GS_NO_CAPTURE(stream);
-    int rc = validate(a);
+    GeomViewRO g;
+    BinViewRO b;
+    ImgViewRO im;
+    const int rc = frame_states(a, geom, geom_bytes, binning, binning_bytes, img, img_bytes, D, &g, &b, &im,
+                                [&]() -> int { return counts ? GS_OK : GS_E_BAD_ARG; });
     if (rc != GS_OK) return rc;
-    if (!geom || !img || !counts || D < 0 || (D > 0 && !binning)) return GS_E_BAD_ARG;
-    const GeomLayout L = geom_layout(a->P);
-    const ImgLayout I = img_layout(a->W, a->H, a->long_lists);
-    const BinLayout B = bin_layout(D);
-    if (geom_bytes < L.total || img_bytes < I.total || (D > 0 && binning_bytes < B.total)) return GS_E_WORKSPACE;
-    const char* g = (const char*)geom;
-    const char* b = (const char*)binning;
-    const char* im = (const char*)img;
-    return launch_pair_stats((const float*)(g + L.rec), D > 0 ? (const uint32_t*)(b + B.point_list) : nullptr,
-                             (const uint32_t*)(im + I.ranges), (const uint32_t*)(im + I.n_contrib), a->W, a->H,
-                             (unsigned long long*)counts, (hipStream_t)stream);
+    return launch_pair_stats(g.rec, b.point_list, im.ranges, im.n_contrib, a->W, a->H, (unsigned long long*)counts, (hipStream_t)stream);
 }
 
 int gs_geom_field(void* geom, int32_t P, int32_t field, void** out) {
     if (!geom || !out || P < 0) return GS_E_BAD_ARG;
-    const GeomLayout L = geom_layout(P);
-    char* g = (char*)geom;
+    const GeomView g = geom_state(geom, P);
     switch (field) {
-        case 0: *out = g + L.depths; break;
-        case 1: *out = g + L.tiles; break;
-        case 2: *out = g + L.rec; break;
-        case 3: *out = g + L.clamped; break;
-        case 4: *out = g + L.val0; break;
-        case 5: *out = g + L.count; break;
+        case GS_GEOM_DEPTHS: *out = g.depths; break;
+        case GS_GEOM_TILES: *out = g.tiles; break;
+        case GS_GEOM_REC: *out = g.rec; break;
+        case GS_GEOM_CLAMPED: *out = g.clamped; break;
+        case GS_GEOM_SORTED_IDX: *out = g.val0; break;
+        case GS_GEOM_COUNT: *out = g.count; break;
         default: return GS_E_BAD_ARG;
     }
     return GS_OK;
 }
 int gs_binning_field(void* binning, int64_t D, int32_t W, int32_t H, int32_t field, void** out) {
     if (!binning || !out || D < 0) return GS_E_BAD_ARG;
-    const BinLayout B = bin_layout(D);
+    const BinView b = bin_state(binning, D);
     (void)W; (void)H;
-    char* b = (char*)binning;
     switch (field) {
-        case 0: *out = b + B.point_list; break;  // (the tile id of every entry follows from the image state's ranges)
-        case 1: *out = b + B.qlist; break;       // quadrant (tile t, q): [4 ranges[t].x + q n_t, ... + qcount[t][q])
+        case GS_BIN_POINT_LIST: *out = b.point_list; break;  // (the tile id of every entry follows from the image state's ranges)
+        case GS_BIN_QLIST: *out = b.qlist; break;            // quadrant (tile t, q): [4 ranges[t].x + q n_t, ... + qcount[t][q])
         default: return GS_E_BAD_ARG;
     }
     return GS_OK;
 }
 int gs_image_field(void* img, int32_t W, int32_t H, int32_t field, void** out) {
     if (!img || !out) return GS_E_BAD_ARG;
-    const ImgLayout I = img_layout(W, H);
-    if (field >= 6 && field <= 9 && !I.cw_rec) return GS_E_BAD_ARG;  // (the chunk-parallel forward's state: small images only)
-    char* m = (char*)img;
+    // (long_lists 0 whatever the render was given: these fields sit in front of everything that depends on it, and the
+    // chunk-parallel forward's exist without it on small images only -- null in the view otherwise)
+    const ImgView im = img_state(img, W, H, 0);
+    void* p = nullptr;
     switch (field) {
-        case 0: *out = m + I.ranges; break;
-        case 1: *out = m + I.n_contrib; break;
-        case 2: *out = m + I.final_T; break;
-        case 3: *out = m + I.tile_nmax; break;
-        case 4: *out = m + I.ncon_c; break;
-        case 5: *out = m + I.order; break;
-        case 6: *out = m + I.cw_hdr; break;    // 16 words: units in use, entries per chunk, .., [4..11] items per XCD
-        case 7: *out = m + I.cw_units; break;  // FWDC_MAX_UNITS x {tile, chunk | chunks << 16}
-        case 8: *out = m + I.cw_flag; break;   // 4 FWDC_MAX_UNITS words: hits + 1 | dead << 31
-        case 9: *out = m + I.cw_rec; break;    // 4 FWDC_MAX_UNITS records of FWDC_SLOTS x 64 floats
-        default: return GS_E_BAD_ARG;
+        case GS_IMG_RANGES: p = im.ranges; break;
+        case GS_IMG_N_CONTRIB: p = im.n_contrib; break;
+        case GS_IMG_FINAL_T: p = im.final_T; break;
+        case GS_IMG_QCOUNT: p = im.qcount; break;
+        case GS_IMG_NCON_C: p = im.ncon_c; break;
+        case GS_IMG_ORDER: p = im.order; break;
+        case GS_IMG_CW_HDR: p = im.cw_hdr; break;      // 16 words: units in use, entries per chunk, .., [4..11] items per XCD
+        case GS_IMG_CW_UNITS: p = im.cw_units; break;  // FWDC_MAX_UNITS x {tile, chunk | chunks << 16}
+        case GS_IMG_CW_FLAG: p = im.cw_flag; break;    // 4 FWDC_MAX_UNITS words: hits + 1 | dead << 31
+        case GS_IMG_CW_REC: p = im.cw_rec; break;      // 4 FWDC_MAX_UNITS records of FWDC_SLOTS x 64 floats
     }
+    if (!p) return GS_E_BAD_ARG;
+    *out = p;
     return GS_OK;
 }
 
@@ -1073,27 +1043,12 @@ int gs_profile_collect(int max, const char** names, float* ms, int32_t* launches
 
 int gs_tuning(const char* name, int value) {
     if (!name) return GS_E_BAD_ARG;
-    tune_defaults();
-    if (strcmp(name, "xcd_map") == 0) { g_tune[GS_TUNE_XCD_MAP].store(value); return GS_OK; }
-    if (strcmp(name, "small_tiles") == 0) { g_tune[GS_TUNE_SMALL_TILES].store(value); return GS_OK; }  // changes the image state's size
-    if (strcmp(name, "ones_fast") == 0) { g_tune[GS_TUNE_ONES_FAST].store(value); return GS_OK; }
-    if (strcmp(name, "shared_qlist") == 0) { g_tune[GS_TUNE_SHARED_QLIST].store(value); return GS_OK; }
-    if (strcmp(name, "fwd4") == 0) { g_tune[GS_TUNE_FWD4].store(value); return GS_OK; }
-    if (strcmp(name, "fwdc_div") == 0) {
-        if (value < 1) return GS_E_BAD_ARG;
-        g_tune[GS_TUNE_FWDC_DIV].store(value);
+    for (const TuneSwitch& t : k_tune) {
+        if (strcmp(name, t.name) != 0) continue;
+        if (t.ok && !t.ok(value)) return GS_E_BAD_ARG;
+        tune_state().v[t.key].store(value);
         return GS_OK;
     }
-    if (strcmp(name, "fwdc_ch") == 0) {
-        if (value < 64 || (value & (value - 1)) != 0) return GS_E_BAD_ARG;
-        g_tune[GS_TUNE_FWDC_CH].store(value);
-        return GS_OK;
-    }
-    if (strcmp(name, "bwd_chunks") == 0) { g_tune[GS_TUNE_BWD_CHUNKS].store(value); return GS_OK; }  // flip between frames only
-    if (strcmp(name, "nt_stores") == 0) { g_tune[GS_TUNE_NT_STORES].store(value); return GS_OK; }
-    if (strcmp(name, "fwd_marks") == 0) { g_tune[GS_TUNE_FWD_MARKS].store(value); return GS_OK; }  // 0: the backward sets its row marks itself (A/B)
-    if (strcmp(name, "bwd_order") == 0) { g_tune[GS_TUNE_BWD_ORDER].store(value); return GS_OK; }  // 0: the backward walks the tiles in the forward's launch order (A/B: + 12 us at config 3)
-    if (strcmp(name, "depth_sort") == 0) { g_tune[GS_TUNE_DEPTH_SORT].store(value); return GS_OK; }  // 1 bucket sort, 0 LSD radix
     return GS_E_BAD_ARG;
 }
 

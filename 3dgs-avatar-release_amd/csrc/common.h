@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/gsplat_mi355.h"
 
 #define TILE 16                 // tile edge in pixels (parity contract: 16x16)
@@ -39,6 +40,9 @@ static inline int ds_buckets(int P) {
 }
 
 #define TB_MAX_SEG 64  // rank segments of the tile-list launches, at most (binning.hip)
+// u64 words of the geom state's count block: the frame's pair count (num_rendered); "a second render's colours are not
+// all ones" (zeroed with the count, set by recolor_kernel); COUNT_ZERO_BYTES: what a frame without Gaussians clears
+enum { COUNT_PAIRS = 0, COUNT_NOT_ONES = 2, COUNT_ZERO_BYTES = 24 };
 struct GeomLayout {
     size_t rec, depths, tiles, clamped, key0, key1, val0, val1, ranklist, chunk_pairs, wsum, wkmin, wkmax, hist, count,
         ds_tmp, ds_tmp2, ds_cnt, ds_pre, ds_tot, ds_loc, ds_grp, ds_range, seg_start, total;
@@ -65,7 +69,7 @@ static inline GeomLayout geom_layout(int P) {
     L.wkmin = take((size_t)L.nwaves * 4);    // smallest / largest depth key of the wave's Gaussians that touch a tile
     L.wkmax = take((size_t)L.nwaves * 4);
     L.hist = take(sort_table_words(n) * 4);
-    L.count = take(64);
+    L.count = take(64);                      // u64 words: COUNT_*
     // bucket depth sort (depth_sort.hip): DS_NB(P) depth buckets + one for the Gaussians that touch no tile
     L.ds_nb = ds_buckets(P);
     L.ds_blocks = (int)((n + DS_ITEMS - 1) / DS_ITEMS);
@@ -159,6 +163,8 @@ int gs_tune_get(int key);
 #define FWDC_SPARSE_PAIRS 524288ull
 #define FWDC_MAX_UNITS 4096
 #define FWDC_MAX_TILES (FWDC_MAX_UNITS / 2)  // marked tiles per frame (each has at least two chunks)
+#define FWDC_Q_WORDS (8 * FWDC_MAX_UNITS * 4)               // [XCD][item] words of the image state's cw_q block ...
+#define FWDC_Q_BYTES ((size_t)FWDC_Q_WORDS * 4 + 64)        // ... and its size with the XCD-mask word behind them
 #ifdef FWDC_PROF
 #define FWDC_SLOTS 9            // (+ a slot of time stamps: tools/fwdc_prof.py)
 #else
@@ -205,8 +211,8 @@ static inline ImgLayout img_layout(int W, int H, int long_lists = 0) {
         L.cw_done = take(nt * 16);
         // [XCD][item of its list]: 1 once a wave has taken the item; behind them one word: the XCDs this frame's launches
         // run on (a bit each)
-        L.cw_q = take((size_t)8 * FWDC_MAX_UNITS * 4 * 4 + 64);
-        L.tile_zero_bytes = L.cw_q + (size_t)8 * FWDC_MAX_UNITS * 4 * 4 + 64 - L.tile_tot;
+        L.cw_q = take(FWDC_Q_BYTES);
+        L.tile_zero_bytes = L.cw_q + FWDC_Q_BYTES - L.tile_tot;
     }
     L.l1_part = take(nt * 16);  // per quadrant: sum |out_color - l1_target| over its pixels (GsFwdArgs.l1_target)
     L.bwd_chunks = fl ? BWD_KMAX : 1;
@@ -217,11 +223,126 @@ static inline ImgLayout img_layout(int W, int H, int long_lists = 0) {
     if (cw) {
         L.cw_hdr = take(64);                                   // [0] units in use, [1] entries per chunk, [4..11] items given to every XCD
         L.cw_units = take((size_t)FWDC_MAX_UNITS * 8);         // {tile, chunk | chunks of the tile << 16}
-        L.cw_items = take((size_t)8 * FWDC_MAX_UNITS * 4 * 4); // [XCD][item]: unit * 4 + quadrant, a tile's items in chunk order
+        L.cw_items = take((size_t)FWDC_Q_WORDS * 4);           // [XCD][item]: unit * 4 + quadrant, a tile's items in chunk order
         L.cw_rec = take((size_t)FWDC_MAX_UNITS * 4 * FWDC_SLOTS * 64 * 4);
     }
     L.total = o;
     return L;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Typed views of the three state buffers: what the layouts above carve, as pointers of the type every field is read
+// and written with.  geom_state / bin_state / img_state are the ONLY places where `base + offset` is cast; the host
+// code (capi.hip) names fields.  A view is built per call, AFTER the tuning switches the image layout depends on are
+// read, and never kept (see the layouts' note).  RO: the caller handed the state over as const -- every member then
+// points to const.  A null base (the binning state of a frame without pairs) gives null members; so does a field the
+// layout leaves out (the chunk-parallel forward's, without fwd4 = 2).
+// ---------------------------------------------------------------------------------------------
+template <bool RO>
+struct StateCarve {
+    typename std::conditional<RO, const char, char>::type* base;
+    StateCarve(typename std::conditional<RO, const void, void>::type* state) : base(static_cast<decltype(base)>(state)) {}
+    template <class T>
+    void operator()(T*& field, size_t offset, bool present = true) const {
+        field = (base && present) ? reinterpret_cast<T*>(base + offset) : nullptr;  // (does not compile from const to non-const)
+    }
+};
+template <bool RO>
+struct GeomViewT {
+    template <class T> using ptr = typename std::conditional<RO, const T, T>::type*;
+    ptr<float> rec, depths;
+    ptr<uint32_t> tiles, clamped, key0, key1, val0, val1;
+    ptr<uint4> ranklist;
+    ptr<uint32_t> chunk_pairs, wsum, wkmin, wkmax, hist;
+    ptr<unsigned long long> count;  // [COUNT_*]
+    ptr<unsigned long long> ds_tmp, ds_tmp2;
+    ptr<uint32_t> ds_cnt, ds_pre, ds_tot, ds_loc, ds_grp, ds_range, seg_start;
+    size_t total;
+    int nwaves, ds_nb, ds_blocks;
+};
+template <bool RO>
+struct BinViewT {
+    template <class T> using ptr = typename std::conditional<RO, const T, T>::type*;
+    ptr<uint32_t> point_list, qlist;
+    ptr<uint4> marks;  // four row-mark words per pair
+    ptr<uint32_t> marks_flag;
+    size_t total;
+};
+template <bool RO>
+struct ImgViewT {
+    template <class T> using ptr = typename std::conditional<RO, const T, T>::type*;
+    ptr<uint32_t> ranges, n_contrib;
+    ptr<float> final_T;
+    ptr<uint32_t> ncon_c, qcount /* ImgLayout::tile_nmax */, order, seg_cnt, tile_tot, all_ones;
+    ptr<uint32_t> cw_flag, cw_done, cw_q, cw_xcc_mask /* the word behind cw_q's items */;
+    ptr<float> l1_part;
+    ptr<float4> ckpt;
+    ptr<uint32_t> ck_start, cw_hdr;
+    ptr<uint2> cw_units;
+    ptr<uint32_t> cw_items;
+    ptr<float> cw_rec;
+    size_t tile_zero_bytes;  // from tile_tot on: what the preprocess kernel clears for the counting pass
+    int cw_clear_words;      // from cw_flag on, to the end of the cw_q block: what a second render of the geometry clears (0: no such state)
+    size_t total;
+    int gx, gy, ntiles, bwd_chunks;
+};
+typedef GeomViewT<false> GeomView;
+typedef GeomViewT<true> GeomViewRO;
+typedef BinViewT<false> BinView;
+typedef BinViewT<true> BinViewRO;
+typedef ImgViewT<false> ImgView;
+typedef ImgViewT<true> ImgViewRO;
+
+template <class Void /* void | const void */>
+static inline GeomViewT<std::is_const<Void>::value> geom_state(Void* base, int P) {
+    constexpr bool RO = std::is_const<Void>::value;
+    const GeomLayout L = geom_layout(P);
+    const StateCarve<RO> at{base};
+    GeomViewT<RO> v;
+    at(v.rec, L.rec); at(v.depths, L.depths); at(v.tiles, L.tiles); at(v.clamped, L.clamped);
+    at(v.key0, L.key0); at(v.key1, L.key1); at(v.val0, L.val0); at(v.val1, L.val1);
+    at(v.ranklist, L.ranklist); at(v.chunk_pairs, L.chunk_pairs);
+    at(v.wsum, L.wsum); at(v.wkmin, L.wkmin); at(v.wkmax, L.wkmax); at(v.hist, L.hist); at(v.count, L.count);
+    at(v.ds_tmp, L.ds_tmp); at(v.ds_tmp2, L.ds_tmp2); at(v.ds_cnt, L.ds_cnt); at(v.ds_pre, L.ds_pre);
+    at(v.ds_tot, L.ds_tot); at(v.ds_loc, L.ds_loc); at(v.ds_grp, L.ds_grp); at(v.ds_range, L.ds_range);
+    at(v.seg_start, L.seg_start);
+    v.total = L.total; v.nwaves = L.nwaves; v.ds_nb = L.ds_nb; v.ds_blocks = L.ds_blocks;
+    return v;
+}
+template <class Void /* void | const void */>
+static inline BinViewT<std::is_const<Void>::value> bin_state(Void* base, int64_t D) {
+    constexpr bool RO = std::is_const<Void>::value;
+    const BinLayout L = bin_layout(D);
+    const StateCarve<RO> at{base};
+    BinViewT<RO> v;
+    at(v.point_list, L.point_list); at(v.qlist, L.qlist); at(v.marks, L.marks); at(v.marks_flag, L.marks_flag);
+    v.total = L.total;
+    return v;
+}
+template <class Void /* void | const void */>
+static inline ImgViewT<std::is_const<Void>::value> img_state(Void* base, int W, int H, int long_lists) {
+    constexpr bool RO = std::is_const<Void>::value;
+    const ImgLayout L = img_layout(W, H, long_lists);
+    const StateCarve<RO> at{base};
+    const bool cw = L.cw_rec != 0;  // (the layout's own condition: few long lists and fwd4 = 2)
+    ImgViewT<RO> v;
+    at(v.ranges, L.ranges); at(v.n_contrib, L.n_contrib); at(v.final_T, L.final_T); at(v.ncon_c, L.ncon_c);
+    at(v.qcount, L.tile_nmax); at(v.order, L.order); at(v.seg_cnt, L.seg_cnt); at(v.tile_tot, L.tile_tot);
+    at(v.all_ones, L.all_ones);
+    at(v.cw_flag, L.cw_flag, cw); at(v.cw_done, L.cw_done, cw); at(v.cw_q, L.cw_q, cw);
+    at(v.cw_xcc_mask, L.cw_q + (size_t)FWDC_Q_WORDS * 4, cw);
+    at(v.l1_part, L.l1_part); at(v.ckpt, L.ckpt); at(v.ck_start, L.ck_start);
+    at(v.cw_hdr, L.cw_hdr, cw); at(v.cw_units, L.cw_units, cw); at(v.cw_items, L.cw_items, cw); at(v.cw_rec, L.cw_rec, cw);
+    v.tile_zero_bytes = L.tile_zero_bytes;
+    v.cw_clear_words = cw ? (int)((L.cw_q + FWDC_Q_BYTES - L.cw_flag) / 4) : 0;
+    v.total = L.total; v.gx = L.gx; v.gy = L.gy; v.ntiles = L.gx * L.gy; v.bwd_chunks = L.bwd_chunks;
+    return v;
+}
+// The one deliberate write into a state its caller passes as read-only: gs_forward_shared's recolouring launch sets the
+// "not all ones" word of the FIRST render's geom state (zero since that render: the numbering kernels clear it with the
+// count), where the render launch behind it and the one-pass backward of both images look for it.
+static inline unsigned long long* not_ones_word(const GeomViewRO& first) {
+    return const_cast<unsigned long long*>(first.count) + COUNT_NOT_ONES;
 }
 
 static inline int radix_passes(int bits) { return (bits + 7) / 8; }
@@ -393,8 +514,6 @@ __device__ __forceinline__ uint32_t pair_count(const PairCount pc) {
     const unsigned long long d = *pc.dev;
     return d <= (unsigned long long)pc.cap ? (uint32_t)d : 0u;
 }
-
-// Process-wide tuning switches (gs_tuning; experiments and A/B runs, not part of the drop-in surface).
 
 // Workgroup -> (tile slot, quadrant) of the render kernels.  Workgroups are dealt round-robin over the 8 XCDs (each
 // with its own L2), so with the plain mapping (slot = b / 4, quadrant = b % 4) the four quadrant waves of one tile land

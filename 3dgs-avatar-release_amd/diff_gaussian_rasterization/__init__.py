@@ -474,7 +474,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.check(L.gs_forward_render(ctypes.byref(a), geom.data_ptr(), geom_bytes, binning.data_ptr(), bin_bytes,
                                                img.data_ptr(), img_bytes, capacity, color.data_ptr(), sptr))
                 cptr = ctypes.c_void_p()
-                _lib.check(L.gs_geom_field(geom.data_ptr(), P, 5, ctypes.byref(cptr)))
+                _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_COUNT, ctypes.byref(cptr)))
                 off = int(cptr.value) - geom.data_ptr()
                 _captured.append((geom[off:off + 8].view(torch.int64), capacity))
                 num_rendered = capacity  # (the frame's own count is only known on the device)

@@ -50,6 +50,11 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
 GS_ADAM_MAX_TENSORS = 16
+# `field` of gs_geom_field / gs_binning_field / gs_image_field (include/gsplat_mi355.h: GsGeomField, GsBinningField, GsImageField)
+GS_GEOM_DEPTHS, GS_GEOM_TILES, GS_GEOM_REC, GS_GEOM_CLAMPED, GS_GEOM_SORTED_IDX, GS_GEOM_COUNT, GS_GEOM_FIELDS = range(7)
+GS_BIN_POINT_LIST, GS_BIN_QLIST, GS_BIN_FIELDS = range(3)
+(GS_IMG_RANGES, GS_IMG_N_CONTRIB, GS_IMG_FINAL_T, GS_IMG_QCOUNT, GS_IMG_NCON_C, GS_IMG_ORDER, GS_IMG_CW_HDR, GS_IMG_CW_UNITS,
+ GS_IMG_CW_FLAG, GS_IMG_CW_REC, GS_IMG_FIELDS) = range(11)
 
 
 class GsAdamTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsAdamTensor

@@ -59,34 +59,34 @@ def forward_state(settings, means3D, opacities, shs=None, colors_precomp=None, s
             return out.value
         gx, gy = (W + 15) // 16, (H + 15) // 16
         g = dict(
-            depths=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, 0), 4 * P, np.float32),
-            tiles_touched=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, 1), 4 * P, np.uint32),
-            rec=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, 2), 48 * P, np.float32).reshape(P, 12),
-            clamped=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, 3), 4 * P, np.uint32),
-            sorted_idx=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, 4), 4 * P, np.uint32),
+            depths=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_DEPTHS), 4 * P, np.float32),
+            tiles_touched=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_TILES), 4 * P, np.uint32),
+            rec=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_REC), 48 * P, np.float32).reshape(P, 12),
+            clamped=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_CLAMPED), 4 * P, np.uint32),
+            sorted_idx=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_SORTED_IDX), 4 * P, np.uint32),
         ) if P > 0 else {}
         b = dict(
-            point_list=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, 0), 4 * D, np.uint32),
+            point_list=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, _lib.GS_BIN_POINT_LIST), 4 * D, np.uint32),
             # the quadrants' compacted lists: quadrant q of tile t at [4 ranges[t, 0] + q n_t, ... + qcount[t, q])
-            qlist=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, 1), 16 * D, np.uint32),
+            qlist=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, _lib.GS_BIN_QLIST), 16 * D, np.uint32),
         ) if D > 0 else dict(point_list=np.zeros(0, np.uint32), qlist=np.zeros(0, np.uint32))
         im = dict(
-            ranges=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 0), 8 * gx * gy, np.uint32).reshape(-1, 2),
-            n_contrib=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 1), 4 * W * H, np.uint32).reshape(H, W),
-            final_T=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 2), 4 * W * H, np.float32).reshape(H, W),
-            qcount=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 3), 16 * gx * gy, np.uint32).reshape(-1, 4),
+            ranges=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_RANGES), 8 * gx * gy, np.uint32).reshape(-1, 2),
+            n_contrib=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_N_CONTRIB), 4 * W * H, np.uint32).reshape(H, W),
+            final_T=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_FINAL_T), 4 * W * H, np.float32).reshape(H, W),
+            qcount=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_QCOUNT), 16 * gx * gy, np.uint32).reshape(-1, 4),
             # launch order of the tiles (heaviest first); bit 31: rendered by four waves per quadrant (small images)
-            order=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 5), 4 * gx * gy, np.uint32),
+            order=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_ORDER), 4 * gx * gy, np.uint32),
         )
         # the chunk-parallel forward's work list and hand-off words (gs_tuning "fwd4" = 2 on a small image; else absent)
         probe = ctypes.c_void_p(0)
-        if L.gs_image_field(img.data_ptr(), W, H, 6, ctypes.byref(probe)) == 0:  # GS_OK
-            hdr = _view(img, field(L.gs_image_field, img.data_ptr(), W, H, 6), 64, np.uint32)
+        if L.gs_image_field(img.data_ptr(), W, H, _lib.GS_IMG_CW_HDR, ctypes.byref(probe)) == 0:  # GS_OK
+            hdr = _view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_HDR), 64, np.uint32)
             nu = int(hdr[0])
             im["chunks"] = dict(
                 hdr=hdr,
-                units=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 7), 8 * nu, np.uint32).reshape(-1, 2),
-                flags=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, 8), 16 * nu, np.uint32))
+                units=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_UNITS), 8 * nu, np.uint32).reshape(-1, 2),
+                flags=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_FLAG), 16 * nu, np.uint32))
     # the tile of every list entry: the lists are stored tile after tile, so the ranges say it (upstream keeps the tile
     # id in the high half of its sort keys)
     r = im["ranges"].astype(np.int64)

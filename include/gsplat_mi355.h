@@ -42,7 +42,7 @@ extern "C" {
  * would wait for the GPU, copy to or store into host memory, or enqueue anything but kernel launches returns
  * GS_E_CAPTURE without enqueuing anything -- it never leaves the capture half-built or faults on replay.  Capture-safe
  * (kernel launches only, every pointer a device pointer, no host wait):
- *   gs_forward_preprocess  with count_host_pinned == NULL (the count stays in the geom state: gs_geom_field 5)
+ *   gs_forward_preprocess  with count_host_pinned == NULL (the count stays in the geom state: gs_geom_field GS_GEOM_COUNT)
  *   gs_forward_render      with a->frame_stats == NULL, at a fixed capacity (a frame whose count exceeds it renders
  *                          empty: read the count afterwards, outside the graph)
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
@@ -464,20 +464,41 @@ int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* t
                          const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
                          float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`:
- *  geom:    0 depths f32[P]        1 tiles_touched u32[P]   2 splat records f32[P,12]
- *           (x, y, conicA, conicB, conicC, opacity, r, g, b, first pair u32, rect_min u32 (x | y<<16), rect_size u32 (w | h<<16))
- *           3 clamped bitmask u32[P]   4 depth-sorted Gaussian index u32[P]   5 num_rendered u64[1]
- *  binning: 0 point_list u32[D] (tile after tile, (depth, index) order inside a tile; tile t owns ranges[t] of it)
- *           1 qlist u32[4 D]: the quadrants' compacted lists as the forward recorded them; quadrant q of tile t (n_t list
- *             entries) owns [4 ranges[t].x + q n_t, ... + n_t), filled up to image field 3's count (at least)
- *  image:   0 ranges u32[tiles,2]   1 n_contrib u32[H,W]   2 final_T f32[H,W]
- *           3 per-quadrant compacted count up to the last contributor u32[tiles,4]
- *           4 per-pixel last contributor in compacted coordinates u32[H,W]
- *           5 launch order of the tiles u32[tiles], heaviest first; bit 31 = rendered by four waves per quadrant, or in chunks
- *           (gs_tuning "fwd4" = 2 only) 6 chunk work header u32[16] (units, entries per chunk, .., [4..11] items per XCD)
- *           7 units u32[.,2] {tile, chunk | chunks of the tile << 16}   8 per (unit, quadrant) hits + 1 | dead << 31
- *           9 per (unit, quadrant) record f32[8,64] */
+/* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
+ * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
+ * GS_E_BAD_ARG). */
+enum GsGeomField {
+    GS_GEOM_DEPTHS = 0,      /* f32[P] */
+    GS_GEOM_TILES = 1,       /* tiles touched u32[P] */
+    GS_GEOM_REC = 2,         /* splat records f32[P,12]: (x, y, conicA, conicB, conicC, opacity, r, g, b, first pair u32,
+                              * rect_min u32 (x | y<<16), rect_size u32 (w | h<<16)) */
+    GS_GEOM_CLAMPED = 3,     /* clamped bitmask u32[P] */
+    GS_GEOM_SORTED_IDX = 4,  /* depth-sorted Gaussian index u32[P] */
+    GS_GEOM_COUNT = 5,       /* num_rendered u64[1] */
+    GS_GEOM_FIELDS = 6
+};
+enum GsBinningField {
+    GS_BIN_POINT_LIST = 0,   /* u32[D]: tile after tile, (depth, index) order inside a tile; tile t owns ranges[t] of it */
+    GS_BIN_QLIST = 1,        /* u32[4 D]: the quadrants' compacted lists as the forward recorded them; quadrant q of tile t
+                              * (n_t list entries) owns [4 ranges[t].x + q n_t, ... + n_t), filled up to GS_IMG_QCOUNT's
+                              * count (at least) */
+    GS_BIN_FIELDS = 2
+};
+enum GsImageField {
+    GS_IMG_RANGES = 0,       /* u32[tiles,2] */
+    GS_IMG_N_CONTRIB = 1,    /* u32[H,W] */
+    GS_IMG_FINAL_T = 2,      /* f32[H,W] */
+    GS_IMG_QCOUNT = 3,       /* per-quadrant compacted count up to the last contributor u32[tiles,4] */
+    GS_IMG_NCON_C = 4,       /* per-pixel last contributor in compacted coordinates u32[H,W] */
+    GS_IMG_ORDER = 5,        /* launch order of the tiles u32[tiles], heaviest first; bit 31 = rendered by four waves per
+                              * quadrant, or in chunks */
+    /* the chunk-parallel forward's state: only with gs_tuning "fwd4" = 2, on images of up to "small_tiles" tiles */
+    GS_IMG_CW_HDR = 6,       /* chunk work header u32[16] (units, entries per chunk, .., [4..11] items per XCD) */
+    GS_IMG_CW_UNITS = 7,     /* units u32[.,2] {tile, chunk | chunks of the tile << 16} */
+    GS_IMG_CW_FLAG = 8,      /* per (unit, quadrant) hits + 1 | dead << 31 */
+    GS_IMG_CW_REC = 9,       /* per (unit, quadrant) record f32[8,64] */
+    GS_IMG_FIELDS = 10
+};
 int gs_geom_field(void* geom, int32_t P, int32_t field, void** out);
 int gs_binning_field(void* binning, int64_t num_rendered, int32_t W, int32_t H, int32_t field, void** out);
 int gs_image_field(void* img, int32_t W, int32_t H, int32_t field, void** out);

@@ -176,3 +176,261 @@ def test_the_entry_switch_of_render_bwd_keeps_its_loads_inside_one_statement():
         if "ds_read_b" in body:
             assert "s_waitcnt lgkmcnt(0)" in body or "GS_ACC_Y" in body
     assert "s_waitcnt lgkmcnt(0)" in src[src.index("#define GS_ACC_Y"):src.index("#define GS_ACC_Y_OUT")]
+
+
+# ---- the frame path's argument handling, pinned (return codes and state-buffer offsets recorded from the library as it
+# was before the state carve moved behind typed views; calls that fail validation return before any HIP call)
+FAKE = 0x100000   # non-null, 16-byte aligned, never dereferenced
+BIG = 1 << 32     # "large enough" for every state of the small frame below (and too small for 2^30 pairs)
+SMALL = 16
+BAD_ARG, EXCLUSIVE, TOO_LARGE, WORKSPACE = -1, -2, -3, -5
+
+
+def _frame_args(lib, P=10, W=64, H=64):
+    a = lib.GsFwdArgs()
+    a.P, a.W, a.H, a.sh_degree, a.M = P, W, H, 0, 1
+    a.bg = a.viewmatrix = a.projmatrix = a.campos = a.means3D = a.opacities = FAKE
+    a.colors_precomp = a.scales = a.rotations = FAKE
+    return a
+
+
+def _grads(lib, **over):
+    g = lib.GsGrads(*([FAKE] * 8))
+    for k, v in over.items():
+        setattr(g, k, v)
+    return g
+
+
+class _Call(object):
+    """One entry point with arguments that pass every check; call(name=value, ...) replaces some of them.  `a_...` keywords
+    set fields of the GsFwdArgs, `gr_...` of the GsGrads, `second_...` of the GsSecondImage (second=None: a null pointer)."""
+
+    def __init__(self, lib, fn, names, **defaults):
+        self.lib, self.fn, self.names, self.defaults = lib, fn, names, defaults
+
+    def __call__(self, **over):
+        lib = self.lib
+        v = dict(self.defaults)
+        a = _frame_args(lib)
+        gr = _grads(lib)
+        second = lib.GsSecondImage(FAKE, FAKE, FAKE, FAKE, BIG, 0)
+        for k, x in over.items():
+            if k.startswith("a_"):
+                setattr(a, k[2:], x)
+            elif k.startswith("gr_"):
+                setattr(gr, k[3:], x)
+            elif k.startswith("second_"):
+                setattr(second, k[7:], x)
+            else:
+                assert k in v, k
+                v[k] = x
+        keep = []  # (host words the library may write before it validates)
+        args = []
+        for n in self.names:
+            x = v[n]
+            if n == "a":
+                x = ctypes.byref(a) if x else None
+            elif n == "gr":
+                x = ctypes.byref(gr) if x else None
+            elif n == "second":
+                x = ctypes.byref(second) if x else None
+            elif x == "word":
+                keep.append(ctypes.c_int64(0))
+                x = ctypes.cast(ctypes.byref(keep[-1]), ctypes.c_void_p) if n == "count" else ctypes.byref(keep[-1])
+            args.append(x)
+        return self.fn(*args)
+
+
+def _entry_points(lib):
+    L = lib.load()
+    states = dict(geom=FAKE, gb=BIG, binning=FAKE, bb=BIG, img=FAKE, ib=BIG, D=100)
+    bwd = dict(a=True, radii=FAKE, out=FAKE, dpix=FAKE, scratch=FAKE, sb=BIG, gr=True, stream=None, **states)
+    bwd_head = ["a", "radii", "geom", "gb", "binning", "bb", "img", "ib", "D", "out", "dpix"]
+    bwd_tail = ["scratch", "sb", "gr", "stream"]
+    return dict(
+        render=_Call(lib, L.gs_forward_render, ["a", "geom", "gb", "binning", "bb", "img", "ib", "D", "out", "stream"],
+                     a=True, out=FAKE, stream=None, **states),
+        forward=_Call(lib, L.gs_forward, ["a", "geom", "gb", "binning", "bb", "D", "img", "ib", "radii", "count", "out", "num",
+                                          "stream"], a=True, radii=FAKE, count="word", out=FAKE, num="word", stream=None, **states),
+        shared=_Call(lib, L.gs_forward_shared, ["a", "geom_src", "img_src", "geom", "gb", "binning", "bb", "img", "ib", "D", "out",
+                                                "stream"], a=True, geom_src=FAKE, img_src=FAKE, out=FAKE, stream=None, **states),
+        backward=_Call(lib, L.gs_backward, bwd_head + bwd_tail, **bwd),
+        with_opacity=_Call(lib, L.gs_backward_with_opacity, bwd_head + ["dopa"] + bwd_tail, dopa=FAKE, **bwd),
+        with_second=_Call(lib, L.gs_backward_with_second, bwd_head + ["second"] + bwd_tail, second=True, **bwd),
+        opacity_image=_Call(lib, L.gs_opacity_image, ["a", "img", "ib", "opacity", "stream"], a=True, img=FAKE, ib=BIG,
+                            opacity=FAKE, stream=None),
+        pair_stats=_Call(lib, L.gs_pair_stats, ["a", "geom", "gb", "binning", "bb", "img", "ib", "D", "counts", "stream"],
+                         a=True, counts=FAKE, stream=None, **states),
+    )
+
+
+# (entry point, what is wrong, expected).  Where two errors apply the comment names the one that wins.
+_both_colours = dict(a_shs=FAKE)  # shs and colors_precomp at once: GS_E_EXCLUSIVE from the common validation
+BOUNDARY_CASES = [
+    ("render", dict(gb=SMALL), WORKSPACE),
+    ("render", dict(bb=SMALL), WORKSPACE),
+    ("render", dict(ib=SMALL), WORKSPACE),
+    ("render", dict(out=None), BAD_ARG),
+    ("render", dict(geom=None), BAD_ARG),
+    ("render", dict(img=None), BAD_ARG),
+    ("render", dict(binning=None), BAD_ARG),
+    ("render", dict(D=-1), BAD_ARG),
+    ("render", dict(D=1 << 30), TOO_LARGE),
+    ("render", dict(a_l1_target=FAKE), BAD_ARG),
+    ("render", dict(a=None), BAD_ARG),
+    ("render", dict(out=None, gb=SMALL), BAD_ARG),                # null pointer before sizes
+    ("render", dict(D=1 << 30, gb=SMALL), TOO_LARGE),             # capacity before sizes
+    ("render", dict(D=1 << 30, a_l1_target=FAKE), BAD_ARG),       # the L1 pair before the capacity
+    ("render", dict(out=None, **_both_colours), EXCLUSIVE),       # the common validation before everything else
+    ("forward", dict(count=None), BAD_ARG),
+    ("forward", dict(num=None), BAD_ARG),
+    ("forward", dict(D=-1), BAD_ARG),
+    ("forward", dict(gb=SMALL), WORKSPACE),
+    ("forward", dict(ib=SMALL), WORKSPACE),
+    ("forward", dict(geom=None), BAD_ARG),
+    ("forward", dict(radii=None), BAD_ARG),
+    ("forward", dict(**_both_colours), EXCLUSIVE),
+    ("forward", dict(count=None, **_both_colours), BAD_ARG),      # its own null checks before the common validation
+    ("forward", dict(geom=None, gb=SMALL), BAD_ARG),
+    ("shared", dict(geom_src=None), BAD_ARG),
+    ("shared", dict(img_src=None), BAD_ARG),
+    ("shared", dict(out=None), BAD_ARG),
+    ("shared", dict(binning=None), BAD_ARG),
+    ("shared", dict(gb=SMALL), WORKSPACE),
+    ("shared", dict(bb=SMALL), WORKSPACE),
+    ("shared", dict(ib=SMALL), WORKSPACE),
+    ("shared", dict(D=1 << 30), WORKSPACE),                       # (no capacity check here: the binning state is too small)
+    ("shared", dict(geom_src=None, ib=SMALL), BAD_ARG),
+    ("shared", dict(geom_src=None, **_both_colours), EXCLUSIVE),
+    ("backward", dict(gr=None), BAD_ARG),
+    ("backward", dict(dpix=None), BAD_ARG),
+    ("backward", dict(radii=None), BAD_ARG),
+    ("backward", dict(scratch=None), BAD_ARG),
+    ("backward", dict(gr_dL_dmeans2D=None), BAD_ARG),
+    ("backward", dict(gr_dL_dscales=None), BAD_ARG),
+    ("backward", dict(gr_dL_drotations=FAKE + 4), BAD_ARG),
+    ("backward", dict(sb=SMALL), WORKSPACE),
+    ("backward", dict(gb=SMALL), WORKSPACE),
+    ("backward", dict(bb=SMALL), WORKSPACE),
+    ("backward", dict(ib=SMALL), WORKSPACE),
+    ("backward", dict(D=1 << 30), WORKSPACE),
+    ("backward", dict(gr_dL_drotations=FAKE + 4, sb=SMALL), BAD_ARG),
+    ("backward", dict(gr=None, **_both_colours), EXCLUSIVE),
+    ("with_opacity", dict(dopa=None), BAD_ARG),
+    ("with_opacity", dict(sb=SMALL), WORKSPACE),
+    ("with_opacity", dict(gr=None), BAD_ARG),
+    ("with_opacity", dict(dopa=None, **_both_colours), BAD_ARG),  # the extra argument before the common validation
+    ("with_opacity", dict(gr=None, sb=SMALL), BAD_ARG),
+    ("with_second", dict(second=None), BAD_ARG),
+    ("with_second", dict(second_colors=None), BAD_ARG),
+    ("with_second", dict(second_img=None), BAD_ARG),
+    ("with_second", dict(ib=SMALL), WORKSPACE),
+    ("with_second", dict(second=None, **_both_colours), BAD_ARG),
+    ("with_second", dict(second_img_bytes=SMALL, sb=SMALL), WORKSPACE),  # the first image's states before the second's
+    ("with_second", dict(second_img_bytes=SMALL, **_both_colours), EXCLUSIVE),
+    ("opacity_image", dict(ib=SMALL), WORKSPACE),
+    ("opacity_image", dict(img=None), BAD_ARG),
+    ("opacity_image", dict(opacity=None), BAD_ARG),
+    ("opacity_image", dict(opacity=None, ib=SMALL), BAD_ARG),
+    ("opacity_image", dict(opacity=None, **_both_colours), EXCLUSIVE),
+    ("pair_stats", dict(ib=SMALL), WORKSPACE),
+    ("pair_stats", dict(gb=SMALL), WORKSPACE),
+    ("pair_stats", dict(bb=SMALL), WORKSPACE),
+    ("pair_stats", dict(counts=None), BAD_ARG),
+    ("pair_stats", dict(D=-1), BAD_ARG),
+    ("pair_stats", dict(D=1 << 30), WORKSPACE),
+    ("pair_stats", dict(counts=None, ib=SMALL), BAD_ARG),
+    ("pair_stats", dict(counts=None, **_both_colours), EXCLUSIVE),
+]
+
+
+def test_frame_entry_points_answer_bad_arguments_as_before(lib):
+    """Null required pointers, every state buffer too small in turn, scratch too small, a capacity of 2^30 pairs, l1_target
+    without l1_loss, misaligned dL_drotations, null `second` / dL_dopacity_img -- and which error wins where two apply."""
+    calls = _entry_points(lib)
+    got = [(name, sorted(over), calls[name](**over)) for name, over, _ in BOUNDARY_CASES]
+    want = [(name, sorted(over), rc) for name, over, rc in BOUNDARY_CASES]
+    print(got)
+    assert got == want
+    assert {name for name, _, _ in BOUNDARY_CASES} == set(calls)
+
+
+def test_second_image_state_is_checked_before_anything_is_enqueued(lib):
+    """gs_backward_with_second: a second image state that is too small, or carved for another long_lists (another number of
+    backward chunks), is GS_E_BAD_ARG with nothing enqueued -- like every other check of the boundary.  (Until the check
+    moved in front of the tile-order launch this returned GS_E_HIP on a machine without a device.)"""
+    calls = _entry_points(lib)
+    assert calls["with_second"](second_img_bytes=SMALL) == BAD_ARG
+    # 1024 x 1024 has 4096 tiles: the chunked backward's checkpoints exist only with long_lists
+    assert calls["with_second"](a_W=1024, a_H=1024, second_long_lists=1) == BAD_ARG
+    assert calls["with_second"](a_W=1024, a_H=1024, a_long_lists=1, second_long_lists=0) == BAD_ARG
+
+
+def _field_offsets(L, fn, n_fields, *shape):
+    out = ctypes.c_void_p(0)
+    offs = []
+    for f in range(n_fields):
+        rc = fn(FAKE, *shape, f, ctypes.byref(out))
+        offs.append(out.value - FAKE if rc == 0 else rc)
+    return offs
+
+
+def test_tuning_switch_names_and_value_rules(lib):
+    L = lib.load()
+    fwd4 = int(os.environ.get("GSPLAT_FWD4", "1"))  # (the process's own setting)
+    defaults = dict(xcd_map=1, depth_sort=1, nt_stores=1, bwd_chunks=1, fwd4=fwd4, small_tiles=2048, shared_qlist=1, ones_fast=1,
+                    bwd_order=1, fwd_marks=1, fwdc_ch=256, fwdc_div=320)
+    try:
+        for name, v in defaults.items():
+            assert L.gs_tuning(name.encode(), v) == 0, name
+        assert L.gs_tuning(b"no_such_switch", 1) == BAD_ARG
+        assert L.gs_tuning(None, 1) == BAD_ARG
+        assert L.gs_tuning(b"fwdc_ch", 100) == BAD_ARG   # not a power of two
+        assert L.gs_tuning(b"fwdc_ch", 32) == BAD_ARG    # below 64
+        assert L.gs_tuning(b"fwdc_div", 0) == BAD_ARG
+        assert L.gs_tuning(b"fwdc_ch", 128) == 0
+        assert L.gs_tuning(b"fwdc_div", 1) == 0
+    finally:
+        for name, v in defaults.items():
+            lib.tuning(name, v)
+
+
+def test_introspection_fields_sit_where_they_did(lib):
+    """Byte offset of every gs_geom_field / gs_binning_field / gs_image_field field inside its state (the state-buffer byte
+    layouts are ABI: debug.py and the tools read them), and GS_E_BAD_ARG for the first number past each range (the last
+    entry of every list).  Image fields 6-9 -- the chunk-parallel forward's state -- exist only with fwd4 = 2 on an image of
+    up to 2048 tiles."""
+    L = lib.load()
+    assert _field_offsets(L, L.gs_geom_field, 7, 10) == [512, 768, 0, 1024, 1792, 70144, BAD_ARG]
+    assert _field_offsets(L, L.gs_geom_field, 7, 200000) == [9600000, 10400000, 0, 11200000, 13600000, 18707200, BAD_ARG]
+    for W, H in ((64, 64), (1024, 1024)):  # (the binning state's carve does not depend on the image)
+        assert _field_offsets(L, L.gs_binning_field, 3, 100, W, H) == [0, 512, BAD_ARG]
+        assert _field_offsets(L, L.gs_binning_field, 3, 5_000_000, W, H) == [0, 20000000, BAD_ARG]
+    small = [0, 256, 16640, 49408, 33024, 49664]
+    large = [0, 32768, 4227072, 12615680, 8421376, 12681216]
+    fwd4 = int(os.environ.get("GSPLAT_FWD4", "1"))  # (the process's own setting)
+    try:
+        lib.tuning("fwd4", 1)
+        assert _field_offsets(L, L.gs_image_field, 11, 64, 64) == small + [BAD_ARG] * 5
+        assert _field_offsets(L, L.gs_image_field, 11, 1024, 1024) == large + [BAD_ARG] * 5
+        lib.tuning("fwd4", 2)
+        assert _field_offsets(L, L.gs_image_field, 11, 64, 64) == small + [1632256, 1632512, 54528, 2189568, BAD_ARG]
+        assert _field_offsets(L, L.gs_image_field, 11, 1024, 1024) == large + [BAD_ARG] * 5
+    finally:
+        lib.tuning("fwd4", fwd4)
+    out = ctypes.c_void_p(0)
+    assert L.gs_geom_field(None, 10, 0, ctypes.byref(out)) == BAD_ARG
+    assert L.gs_geom_field(FAKE, -1, 0, ctypes.byref(out)) == BAD_ARG
+    assert L.gs_binning_field(FAKE, -1, 64, 64, 0, ctypes.byref(out)) == BAD_ARG
+    assert L.gs_image_field(FAKE, 64, 64, 0, None) == BAD_ARG
+
+
+def test_field_names_of_the_binding_are_the_header_s(lib):
+    """The GS_GEOM_* / GS_BIN_* / GS_IMG_* constants of _lib.py mirror the enums of include/gsplat_mi355.h."""
+    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
+    names = re.findall(r"\b(GS_(?:GEOM|BIN|IMG)_[A-Z0-9_]+)\s*=\s*(\d+)", header)
+    assert len(names) == 6 + 2 + 10 + 3  # fields + the three counts
+    for name, value in names:
+        assert getattr(lib, name) == int(value), name
+    assert (lib.GS_GEOM_FIELDS, lib.GS_BIN_FIELDS, lib.GS_IMG_FIELDS) == (6, 2, 10)
+    assert (lib.GS_GEOM_COUNT, lib.GS_IMG_ORDER, lib.GS_IMG_CW_REC) == (5, 5, 9)

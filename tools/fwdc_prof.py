@@ -69,15 +69,15 @@ def main():
             _lib.check(L.gs_image_field(img.data_ptr(), W, H, which, ctypes.byref(out)))
             off = out.value - img.data_ptr()
             return img[off:off + nbytes].cpu().numpy().view(dtype).copy()
-        hdr = field(6, 64, np.uint32)
+        hdr = field(_lib.GS_IMG_CW_HDR, 64, np.uint32)
         nunits, ch = int(hdr[0]), int(hdr[1])
         print("units %d, entries per chunk %d, tiles per XCD %s" % (nunits, ch, hdr[4:12].tolist()))
         if nunits == 0:
             return
-        units = field(7, 8 * nunits, np.uint32).reshape(-1, 2)
-        flags = field(8, 16 * nunits, np.uint32)
+        units = field(_lib.GS_IMG_CW_UNITS, 8 * nunits, np.uint32).reshape(-1, 2)
+        flags = field(_lib.GS_IMG_CW_FLAG, 16 * nunits, np.uint32)
         SL = 9
-        rec = field(9, nunits * 4 * SL * 64 * 4, np.uint32).reshape(nunits * 4, SL, 64)
+        rec = field(_lib.GS_IMG_CW_REC, nunits * 4 * SL * 64 * 4, np.uint32).reshape(nunits * 4, SL, 64)
     ts = rec[:, 8, :6].astype(np.int64)          # [item][6]
     meta = rec[:, 8, 6]
     xcc, blk = meta & 0xFF, meta >> 8
