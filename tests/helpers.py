@@ -99,12 +99,14 @@ def ssim_float64(img1, img2):
     return float(v.detach()), a.grad[0].numpy()
 
 
-def covariance_float64(scaling, modifier, rotation, g6):
+def covariance_float64(scaling, modifier, rotation, g6, dtype=None):
     """Float64 torch restatement of scene/gaussian_model.py:28-32 (+ general_utils.py:73-108,194-207) with
-    autograd: returns (cov6, d/dscaling, d/drotation) for the upstream gradient g6."""
+    autograd: returns (cov6, d/dscaling, d/drotation) for the upstream gradient g6.  `dtype=torch.float32` runs the same
+    lines in the reference's own precision (what an fp32 evaluation of this chain loses, as a yardstick)."""
     import torch
-    s = torch.from_numpy(np.asarray(scaling, np.float32)).double().requires_grad_(True)
-    r = torch.from_numpy(np.asarray(rotation, np.float32)).double().requires_grad_(True)
+    dtype = dtype or torch.float64
+    s = torch.from_numpy(np.asarray(scaling, np.float32)).to(dtype).requires_grad_(True)
+    r = torch.from_numpy(np.asarray(rotation, np.float32)).to(dtype).requires_grad_(True)
     if r.shape[-1] == 4:
         q = r / torch.sqrt((r * r).sum(1))[:, None]
         w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
@@ -116,7 +118,7 @@ def covariance_float64(scaling, modifier, rotation, g6):
     L = R @ torch.diag_embed(modifier * s)
     S = L @ L.transpose(1, 2)
     cov = torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1)
-    (cov * torch.from_numpy(np.asarray(g6, np.float32)).double()).sum().backward()
+    (cov * torch.from_numpy(np.asarray(g6, np.float32)).to(dtype)).sum().backward()
     return cov.detach().numpy(), s.grad.numpy(), r.grad.numpy()
 
 

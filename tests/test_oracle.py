@@ -199,6 +199,40 @@ def test_backward_matches_float64_autograd(oracle, color_mode, cov_mode, deg, bg
         assert np.abs(ref).max() > 0, name
 
 
+@pytest.mark.parametrize("deg,M", [(0, 16), (1, 16), (2, 16), (0, 4), (1, 7), (2, 12)])
+def test_backward_matches_float64_autograd_with_more_coefficients_than_the_degree_uses(oracle, deg, M):
+    """The active degree and the stored coefficient count are independent arguments ((deg+1)^2 <= M <= 16; the reference
+    model stores 16 from the first iteration and raises the degree every 1000, scene/gaussian_model.py:159-163): the
+    oracle with M above (deg+1)^2 against float64 autograd at the bars of test_backward_matches_float64_autograd, and
+    the gradient of every coefficient above the degree exactly zero.  The coefficients above the degree are random and
+    non-zero: none of them may enter a sum."""
+    n, W, H = 300, 48, 32
+    cloud, cam = helpers.cloud_and_camera(n, W, H, sh_degree=3, seed=11, scale_mul=1.5)
+    cloud.shs = cloud.shs[:, :M].contiguous()
+    cloud.sh_degree = deg
+    cloud.shs[:, 0] -= 1.2 * (torch.arange(n) % 7 == 0).float()[:, None]  # some colours clamp at 0
+    bg = (0.3, 0.6, 0.1)
+    sc = helpers.oracle_scene(cloud, cam, bg=bg)
+    assert (sc.sh_degree, sc.M) == (deg, M)
+    fw = oracle.forward(sc)
+    gimg = torch.randn(3, H, W, generator=torch.Generator().manual_seed(2)).numpy().astype(np.float32)
+    gr = oracle.backward(sc, fw, gimg)
+    color, radii, dg, aux = _dense_grads(sc, cloud, cam, gimg, "sh", "scale_rot", bg)
+    assert np.array_equal(radii, fw["radii"])
+    assert np.abs(color - fw["color"]).max() < 5e-6
+    assert fw["geom"]["clamped"].sum() > 0
+    for name in dg:
+        ref = dg[name]
+        got = gr[name].reshape(ref.shape)
+        err = helpers.rel_to_max(got, ref)
+        assert err < 2e-4, (name, err)
+        assert np.abs(ref).max() > 0, name
+    nb = (deg + 1) ** 2
+    assert gr["sh"].shape == (n, M, 3) and np.abs(cloud.shs[:, nb:].numpy()).min() > 0
+    assert (gr["sh"][:, nb:, :] == 0).all() and (dg["sh"][:, nb:, :] == 0).all()
+    assert np.abs(gr["sh"][:, :nb, :]).max() > 0
+
+
 def test_backward_scale_modifier_semantics(oracle):
     """dL/dscale is taken w.r.t. mod*scale (the reference kernel drops the factor; SURVEY A8 vi)."""
     n, W, H = 150, 32, 32
@@ -332,6 +366,20 @@ def test_build_covariance_oracle_vs_float64_autograd(oracle, matrix):
     s = np.array([[1, 2, 3]] * 4, np.float32)
     c = oracle.build_covariance(s, 0.5, ident)
     assert np.allclose(c, [[0.25, 0, 0, 1.0, 0, 2.25]] * 4)
+
+
+def test_build_covariance_fp32_yardstick_of_the_gpu_test_is_what_it_quotes(oracle):
+    """tests/test_gpu_sh_layouts.py bounds the covariance kernel's per-row error by four times what the reference's own
+    lines lose in torch float32 against float64 on the same inputs, and quotes those numbers as constants: re-measured
+    here (within a factor of two: another CPU's float32 matrix products may round in another order).  The oracle itself
+    evaluates in double and rounds once: at most half an fp32 ulp, 6e-8, per row."""
+    import test_gpu_sh_layouts as t
+    got = t.measure_fp32_row_err()
+    assert set(got) == set(t.COV_ROW_ERR_OF_FP32)
+    for key, quoted in t.COV_ROW_ERR_OF_FP32.items():
+        assert 0.5 * quoted <= got[key] <= 2.0 * quoted, (key, got[key], quoted)
+    for key, v in t.measure_fp32_row_err(oracle.build_covariance).items():
+        assert v <= 2.0 ** -24 * 1.0001, (key, v)
 
 
 def test_sh2rgb_oracle_vs_reference_golden_and_float64_autograd(oracle):
