@@ -924,6 +924,48 @@ int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* t
                                     dL_drotation, workspace, (hipStream_t)stream);
 }
 
+// ---- SMPL pose correction (pose.hip)
+static bool pose_a4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+static bool pose_req(const void* p) { return p && pose_a4(p); }
+static int pose_validate(const GsPoseArgs* a) {
+    if (!a || a->V < 1 || a->NB < 1 || a->NB > GS_POSE_MAX_BETAS) return GS_E_BAD_ARG;
+    for (int i = 1; i < GS_POSE_BONES; i++)
+        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
+    if (!pose_req(a->J_shapedirs) || !pose_req(a->root_orient) || !pose_req(a->pose_body) || !pose_req(a->pose_hand) ||
+        !pose_a4(a->rots_gt))
+        return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_pose_workspace_bytes(int32_t V, size_t* out) {
+    if (!out || V < 1) return GS_E_BAD_ARG;
+    *out = pose_workspace_bytes(V);
+    return GS_OK;
+}
+int gs_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone_transforms, float* loss_pose, float* state,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = pose_validate(a)) return rc;
+    if (!pose_req(a->v_template) || !pose_req(a->shapedirs) || !pose_req(a->J_template) || !pose_req(a->betas) ||
+        !pose_req(a->trans) || !pose_req(rots) || !pose_req(Jtrs) || !pose_req(bone_transforms) || !pose_req(state) ||
+        !pose_a4(loss_pose) || (a->rots_gt && !loss_pose))
+        return GS_E_BAD_ARG;
+    if (!workspace || ((uintptr_t)workspace & 7u)) return GS_E_BAD_ARG;
+    if (workspace_bytes < pose_workspace_bytes(a->V)) return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_pose_forward(a, rots, Jtrs, bone_transforms, loss_pose, state, workspace, (hipStream_t)stream);
+}
+int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_drots, const float* dL_dJtrs,
+                     const float* dL_dbone_transforms, const float* dL_dloss_pose, float* dL_dbetas, float* dL_droot_orient,
+                     float* dL_dpose_body, float* dL_dpose_hand, float* dL_dtrans, void* stream) {
+    if (const int rc = pose_validate(a)) return rc;
+    if (!pose_req(state) || !pose_a4(dL_drots) || !pose_a4(dL_dJtrs) || !pose_a4(dL_dbone_transforms) || !pose_a4(dL_dloss_pose) ||
+        !pose_a4(dL_dbetas) || !pose_a4(dL_droot_orient) || !pose_a4(dL_dpose_body) || !pose_a4(dL_dpose_hand) || !pose_a4(dL_dtrans))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_dbetas && !dL_droot_orient && !dL_dpose_body && !dL_dpose_hand && !dL_dtrans) return GS_OK;
+    return launch_pose_backward(a, state, dL_drots, dL_dJtrs, dL_dbone_transforms, dL_dloss_pose, dL_dbetas, dL_droot_orient,
+                                dL_dpose_body, dL_dpose_hand, dL_dtrans, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

@@ -680,6 +680,13 @@ int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, c
 int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
                              const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
                              void* workspace, hipStream_t s);
+// SMPL pose correction (pose.hip; the spec is at its top)
+size_t pose_workspace_bytes(int V);
+int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone, float* loss, float* state, void* workspace,
+                        hipStream_t s);
+int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g_rots, const float* g_Jtrs, const float* g_bone,
+                         const float* g_loss, float* dbetas, float* droot, float* dbody, float* dhand, float* dtrans,
+                         hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

@@ -45,7 +45,8 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_aiap_workspace_bytes", "gs_aiap_forward", "gs_aiap_backward",
            "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward",
            "gs_skin_weights_forward", "gs_skin_weights_backward", "gs_skinning_workspace_bytes", "gs_skinning_forward",
-           "gs_skinning_backward"]
+           "gs_skinning_backward",
+           "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -88,6 +89,15 @@ GS_HASHGRID_MAX_LEVELS = 32  # include/gsplat_mi355.h
 
 GS_SKIN_BONES = 24  # include/gsplat_mi355.h
 GS_SKIN_HIERARCHICAL, GS_SKIN_SOFTMAX, GS_SKIN_WEIGHTS = 0, 1, 2
+
+
+GS_POSE_BONES, GS_POSE_MAX_BETAS, GS_POSE_STATE_FLOATS = 24, 16, 512  # include/gsplat_mi355.h
+
+
+class GsPoseArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsPoseArgs
+    _fields_ = [("V", c_int32), ("NB", c_int32), ("parents", c_int32 * GS_POSE_BONES)] + [
+        (n, c_void_p) for n in ("v_template", "shapedirs", "J_template", "J_shapedirs", "betas", "root_orient", "pose_body",
+                                "pose_hand", "trans", "rots_gt")]
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -175,6 +185,10 @@ def load():
                                           c_void_p]
         L.gs_skinning_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_pose_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
+        L.gs_pose_forward.argtypes = [POINTER(GsPoseArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]
+        L.gs_pose_backward.argtypes = [POINTER(GsPoseArgs)] + [c_void_p] * 11
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

@@ -49,7 +49,7 @@ extern "C" {
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
- *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward
+ *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -463,6 +463,42 @@ int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tf
 int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
                          const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
                          float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- SMPL pose correction of `pose_correction: direct` (models/pose_correction/pose_correction.py:
+ * DirectPoseOptimization.pose_correct through PoseCorrection._forward_smpl, get_transforms_02v and
+ * models/pose_correction/lbs.py), batch 1, 24 joints.  The full semantics (rest joints, shape statistics, Rodrigues, the
+ * kinematic chain, the star-pose transforms, the loss and every gradient) are spelled out at the top of csrc/pose.hip.
+ * All arrays are fp32, row-major, contiguous device arrays; `parents` travels by value (host int32; entry 0 is ignored).
+ * GsPoseArgs: v_template [V, 3], shapedirs [V, 3, NB], J_template [24, 3] = J_regressor v_template and J_shapedirs
+ *   [24, 3, NB] = J_regressor shapedirs (folded once by the caller); betas [NB], root_orient [3], pose_body [63],
+ *   pose_hand [6], trans [3]; rots_gt [24, 9] or NULL (no loss).
+ * gs_pose_forward (two launches): rots [24, 9] (row 0 the identity), Jtrs [24, 3], bone_transforms [24, 4, 4], loss_pose
+ *   (one float; required with rots_gt, else ignored), and `state` (GS_POSE_STATE_FLOATS floats) for the backward.
+ *   `workspace`: gs_pose_workspace_bytes(V) bytes, 8-byte aligned (the per-block partials of the vertex pass).
+ * gs_pose_backward (one launch; reads `state`, never the vertices; of GsPoseArgs it uses NB, parents, J_shapedirs,
+ *   root_orient, pose_body, pose_hand and rots_gt): from dL_drots [24, 9], dL_dJtrs [24, 3], dL_dbone_transforms
+ *   [24, 4, 4] (rows 3 ignored) and dL_dloss_pose (one DEVICE float), any of them NULL = zero, to dL_dbetas [NB],
+ *   dL_droot_orient [3], dL_dpose_body [63], dL_dpose_hand [6], dL_dtrans [3], any of them NULL = not wanted.  Every sum
+ *   has one fixed order (no atomics: bitwise reproducible).
+ * GS_E_BAD_ARG (before any HIP call): a NULL args, V < 1, NB outside 1..GS_POSE_MAX_BETAS, parents[i] outside
+ * 0..i-1 for some i >= 1, a NULL required pointer or a misaligned one (fp32 alignment; the workspace 8 bytes).
+ * GS_E_WORKSPACE: the workspace is smaller than gs_pose_workspace_bytes(V). ---- */
+#define GS_POSE_BONES 24
+#define GS_POSE_MAX_BETAS 16
+#define GS_POSE_STATE_FLOATS 512
+typedef struct GsPoseArgs {
+    int32_t V, NB;
+    int32_t parents[GS_POSE_BONES];
+    const float *v_template, *shapedirs, *J_template, *J_shapedirs;
+    const float *betas, *root_orient, *pose_body, *pose_hand, *trans;
+    const float* rots_gt;
+} GsPoseArgs;
+int gs_pose_workspace_bytes(int32_t V, size_t* out);
+int gs_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone_transforms, float* loss_pose, float* state,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_drots, const float* dL_dJtrs,
+                     const float* dL_dbone_transforms, const float* dL_dloss_pose, float* dL_dbetas, float* dL_droot_orient,
+                     float* dL_dpose_body, float* dL_dpose_hand, float* dL_dtrans, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
  * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
