@@ -966,6 +966,88 @@ int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_dr
                                 dL_dpose_body, dL_dpose_hand, dL_dtrans, (hipStream_t)stream);
 }
 
+// ---- the non-rigid deformer around its MLP (nonrigid.hip)
+static bool nr_a16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static int pose_enc_validate(const GsPoseEncArgs* a) {
+    if (!a || a->d < 1 || a->d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
+    for (int i = 1; i < GS_POSE_ENC_JOINTS; i++)
+        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
+    if (!pose_req(a->W0)) return GS_E_BAD_ARG;
+    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
+        if (!pose_req(a->W1[j]) || !pose_req(a->W2[j])) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_pose_encoder_grad_floats(int32_t d, size_t* out) {
+    if (!out || d < 1 || d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
+    *out = pose_encoder_grad_floats(d);
+    return GS_OK;
+}
+int gs_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, void* stream) {
+    if (const int rc = pose_enc_validate(a)) return rc;
+    if (!pose_req(a->rots) || !pose_req(a->Jtrs) || !pose_req(a->b0) || !pose_req(out) || !pose_req(state)) return GS_E_BAD_ARG;
+    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
+        if (!pose_req(a->b1[j]) || !pose_req(a->b2[j])) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_pose_encoder_forward(a, out, state, (hipStream_t)stream);
+}
+int gs_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* dL_dout, float* dL_dparams,
+                             float* dL_drots, float* dL_dJtrs, void* stream) {
+    if (const int rc = pose_enc_validate(a)) return rc;
+    if (!pose_req(state) || !pose_req(dL_dout) || !pose_a4(dL_dparams) || !pose_a4(dL_drots) || !pose_a4(dL_dJtrs))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_dparams && !dL_drots && !dL_dJtrs) return GS_OK;
+    return launch_pose_encoder_backward(a, state, dL_dout, dL_dparams, dL_drots, dL_dJtrs, (hipStream_t)stream);
+}
+static bool nr_shape_ok(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset) {
+    return N >= 0 && D >= 10 && D <= GS_NONRIGID_MAX_D &&
+           (scale_offset == GS_NR_SCALE_LOGIT || scale_offset == GS_NR_SCALE_EXP || scale_offset == GS_NR_SCALE_ZERO) &&
+           (rot_offset == GS_NR_ROT_ADD || rot_offset == GS_NR_ROT_MULT);
+}
+int gs_nonrigid_workspace_bytes(int32_t N, int32_t D, size_t* out) {
+    if (!out || N < 0 || D < 10 || D > GS_NONRIGID_MAX_D) return GS_E_BAD_ARG;
+    *out = nonrigid_workspace_bytes(N, D);
+    return GS_OK;
+}
+int gs_nonrigid_apply_forward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                              const float* xyz, const float* scaling, const float* rotation, float* xyz_out,
+                              float* scaling_out, float* rotation_out, float* feature, float* losses, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!deltas || !xyz || !rotation || !xyz_out || !rotation_out || (D > 10 && !feature)) return GS_E_BAD_ARG;
+    if (scale_offset != GS_NR_SCALE_ZERO && (!scaling || !scaling_out)) return GS_E_BAD_ARG;
+    if (scaling_out && !scaling) return GS_E_BAD_ARG;
+    if (!nr_a16(deltas) || !nr_a16(rotation) || !nr_a16(rotation_out) || !nr_a16(feature) || !pose_a4(xyz) || !pose_a4(scaling) ||
+        !pose_a4(xyz_out) || !pose_a4(scaling_out) || !pose_a4(losses))
+        return GS_E_BAD_ARG;
+    if (losses) {
+        if (!workspace || !pose_a4(workspace)) return GS_E_BAD_ARG;
+        if (workspace_bytes < nonrigid_workspace_bytes(N, D)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_nonrigid_apply_forward(N, D, scale_offset, rot_offset, deltas, xyz, scaling, rotation, xyz_out, scaling_out,
+                                         rotation_out, D > 10 ? feature : nullptr, losses, workspace, (hipStream_t)stream);
+}
+int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                               const float* scaling, const float* rotation, const float* dL_dxyz_out,
+                               const float* dL_dscaling_out, const float* dL_drotation_out, const float* dL_dfeature,
+                               const float* dL_dnr_xyz, const float* dL_dnr_scale, const float* dL_dnr_rot,
+                               float* dL_ddeltas, float* dL_dscaling, float* dL_drotation, void* stream) {
+    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!deltas || (scale_offset == GS_NR_SCALE_EXP && !scaling) || (rot_offset == GS_NR_ROT_MULT && !rotation)) return GS_E_BAD_ARG;
+    if (!nr_a16(deltas) || !nr_a16(rotation) || !nr_a16(dL_drotation_out) || !nr_a16(dL_dfeature) || !nr_a16(dL_ddeltas) ||
+        !nr_a16(dL_drotation) || !pose_a4(scaling) || !pose_a4(dL_dxyz_out) || !pose_a4(dL_dscaling_out) || !pose_a4(dL_dnr_xyz) ||
+        !pose_a4(dL_dnr_scale) || !pose_a4(dL_dnr_rot) || !pose_a4(dL_dscaling))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_ddeltas && !dL_dscaling && !dL_drotation) return GS_OK;
+    return launch_nonrigid_apply_backward(N, D, scale_offset, rot_offset, deltas, scaling, rotation, dL_dxyz_out, dL_dscaling_out,
+                                          dL_drotation_out, D > 10 ? dL_dfeature : nullptr, dL_dnr_xyz, dL_dnr_scale, dL_dnr_rot,
+                                          dL_ddeltas, dL_dscaling, dL_drotation, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

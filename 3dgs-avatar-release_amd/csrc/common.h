@@ -687,6 +687,19 @@ int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bo
 int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g_rots, const float* g_Jtrs, const float* g_bone,
                          const float* g_loss, float* dbetas, float* droot, float* dbody, float* dhand, float* dtrans,
                          hipStream_t s);
+// the non-rigid deformer around its MLP (nonrigid.hip; the spec is at its top)
+size_t pose_encoder_grad_floats(int d);
+int launch_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, hipStream_t s);
+int launch_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* g_out, float* dparams, float* drots,
+                                 float* dJtrs, hipStream_t s);
+size_t nonrigid_workspace_bytes(int N, int D);
+int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, const float* deltas, const float* xyz, const float* scaling,
+                                  const float* rot, float* xyz_o, float* scal_o, float* rot_o, float* feat, float* losses,
+                                  void* workspace, hipStream_t s);
+int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const float* deltas, const float* scaling, const float* rot,
+                                   const float* g_xyz, const float* g_scal, const float* g_rot, const float* g_feat,
+                                   const float* g_nrx, const float* g_nrs, const float* g_nrr, float* ddeltas, float* dscal,
+                                   float* drot, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

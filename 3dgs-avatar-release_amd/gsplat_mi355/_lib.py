@@ -46,7 +46,9 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward",
            "gs_skin_weights_forward", "gs_skin_weights_backward", "gs_skinning_workspace_bytes", "gs_skinning_forward",
            "gs_skinning_backward",
-           "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward"]
+           "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward",
+           "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
+           "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -98,6 +100,18 @@ class GsPoseArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsPoseArgs
     _fields_ = [("V", c_int32), ("NB", c_int32), ("parents", c_int32 * GS_POSE_BONES)] + [
         (n, c_void_p) for n in ("v_template", "shapedirs", "J_template", "J_shapedirs", "betas", "root_orient", "pose_body",
                                 "pose_hand", "trans", "rots_gt")]
+
+
+GS_POSE_ENC_JOINTS, GS_POSE_ENC_MAX_DIM, GS_POSE_ENC_STATE_FLOATS = 24, 16, 1392  # include/gsplat_mi355.h
+GS_NONRIGID_MAX_D = 2048
+GS_NR_SCALE_LOGIT, GS_NR_SCALE_EXP, GS_NR_SCALE_ZERO = 0, 1, 2
+GS_NR_ROT_ADD, GS_NR_ROT_MULT = 0, 1
+
+
+class GsPoseEncArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsPoseEncArgs
+    _fields_ = [("d", c_int32), ("parents", c_int32 * GS_POSE_ENC_JOINTS)] + [
+        (n, c_void_p) for n in ("rots", "Jtrs", "W0", "b0")] + [
+        (n, c_void_p * GS_POSE_ENC_JOINTS) for n in ("W1", "b1", "W2", "b2")]
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -189,6 +203,12 @@ def load():
         L.gs_pose_forward.argtypes = [POINTER(GsPoseArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]
         L.gs_pose_backward.argtypes = [POINTER(GsPoseArgs)] + [c_void_p] * 11
+        L.gs_pose_encoder_grad_floats.argtypes = [c_int32, POINTER(c_size_t)]
+        L.gs_pose_encoder_forward.argtypes = [POINTER(GsPoseEncArgs), c_void_p, c_void_p, c_void_p]
+        L.gs_pose_encoder_backward.argtypes = [POINTER(GsPoseEncArgs)] + [c_void_p] * 6
+        L.gs_nonrigid_workspace_bytes.argtypes = [c_int32, c_int32, POINTER(c_size_t)]
+        L.gs_nonrigid_apply_forward.argtypes = [c_int32] * 4 + [c_void_p] * 10 + [c_size_t, c_void_p]
+        L.gs_nonrigid_apply_backward.argtypes = [c_int32] * 4 + [c_void_p] * 14
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

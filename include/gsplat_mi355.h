@@ -49,7 +49,8 @@ extern "C" {
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
- *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward
+ *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward,
+ *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
@@ -499,6 +500,69 @@ int gs_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone_t
 int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_drots, const float* dL_dJtrs,
                      const float* dL_dbone_transforms, const float* dL_dloss_pose, float* dL_dbetas, float* dL_droot_orient,
                      float* dL_dpose_body, float* dL_dpose_hand, float* dL_dtrans, void* stream);
+
+/* ---- the non-rigid deformer around its MLP (models/deformer/non_rigid.py MLP / HashGridwithMLP): the hierarchical pose
+ * encoder in front of it (models/network_utils.py HierarchicalPoseEncoder.forward, rel_joints = False, batch 1, 24
+ * joints) and the application of the MLP's output behind it.  The full semantics, every gradient included, are spelled
+ * out at the top of csrc/nonrigid.hip.  All arrays are fp32, row-major, contiguous.
+ *
+ * GsPoseEncArgs: d = dim_per_joint in 1..GS_POSE_ENC_MAX_DIM (m = 13 + d); the kinematic tree by value (parents[i] < i
+ *   for i >= 1, entry 0 ignored); rots [24, 9], Jtrs [24, 3]; and the ADDRESSES of the 98 parameter tensors, nn.Linear
+ *   layouts: W0 [d, 288], b0 [d], W1[j] [m, m], b1[j] [m], W2[j] [d, m], b2[j] [d].  The struct is handed to the kernel
+ *   by value: there is no pointer table in device memory.
+ * gs_pose_encoder_forward (one launch, one workgroup): out [24 d] (the out_j in joint order) and `state`
+ *   (GS_POSE_ENC_STATE_FLOATS floats: in_j and h_j) for the backward.
+ * gs_pose_encoder_backward (one launch, one workgroup; reads `state`, the parameters, d and parents): from dL_dout
+ *   [24 d] to dL_dparams (gs_pose_encoder_grad_floats(d) floats, packed W0 | b0 | (W1_j | b1_j | W2_j | b2_j) for
+ *   j = 0..23), dL_drots [24, 9] and dL_dJtrs [24, 3], any of the three NULL = not wanted.  Every sum has one fixed
+ *   order: bitwise reproducible.
+ *
+ * gs_nonrigid_apply_forward (one launch, plus one of three workgroups with `losses`): deltas [N, D], D = 10 + F in
+ *   10..GS_NONRIGID_MAX_D, xyz [N, 3], scaling [N, 3], rotation [N, 4] -> xyz_out, scaling_out, rotation_out, feature
+ *   [N, F] (required when F > 0) and losses [3] = (nr_xyz, nr_scale, nr_rot) (NULL = not wanted; then no workspace is
+ *   needed).  scale_offset: GS_NR_SCALE_*; rot_offset: GS_NR_ROT_*.  With GS_NR_SCALE_ZERO `scaling` and `scaling_out`
+ *   may both be NULL (scaling' is scaling itself).  `deltas` is never written (the reference overwrites its column 6
+ *   with 1 in GS_NR_ROT_MULT mode).  `workspace`: gs_nonrigid_workspace_bytes(N, D) bytes.
+ * gs_nonrigid_apply_backward (one launch): from dL_dxyz_out, dL_dscaling_out, dL_drotation_out, dL_dfeature and the three
+ *   DEVICE floats dL_dnr_xyz, dL_dnr_scale, dL_dnr_rot, any of them NULL = zero, to dL_ddeltas [N, D] (every element
+ *   written, zeros included), dL_dscaling and dL_drotation, any of them NULL = not wanted.  dL/dxyz is dL_dxyz_out.
+ * N == 0 does nothing.  GS_E_BAD_ARG (before any HIP call): a NULL args, d outside 1..GS_POSE_ENC_MAX_DIM, parents[i]
+ * outside 0..i-1 for some i >= 1, N < 0, D outside 10..GS_NONRIGID_MAX_D, an unknown mode, a NULL required pointer or a
+ * misaligned one (16 bytes for deltas, rotation, rotation_out, feature and their gradients, else fp32 alignment).
+ * GS_E_WORKSPACE: the workspace is smaller than gs_nonrigid_workspace_bytes(N, D). ---- */
+#define GS_POSE_ENC_JOINTS 24
+#define GS_POSE_ENC_MAX_DIM 16
+#define GS_POSE_ENC_STATE_FLOATS 1392
+typedef struct GsPoseEncArgs {
+    int32_t d;
+    int32_t parents[GS_POSE_ENC_JOINTS];
+    const float *rots, *Jtrs;
+    const float *W0, *b0;
+    const float* W1[GS_POSE_ENC_JOINTS];
+    const float* b1[GS_POSE_ENC_JOINTS];
+    const float* W2[GS_POSE_ENC_JOINTS];
+    const float* b2[GS_POSE_ENC_JOINTS];
+} GsPoseEncArgs;
+int gs_pose_encoder_grad_floats(int32_t d, size_t* out);
+int gs_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, void* stream);
+int gs_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* dL_dout, float* dL_dparams,
+                             float* dL_drots, float* dL_dJtrs, void* stream);
+#define GS_NONRIGID_MAX_D 2048
+#define GS_NR_SCALE_LOGIT 0
+#define GS_NR_SCALE_EXP 1
+#define GS_NR_SCALE_ZERO 2
+#define GS_NR_ROT_ADD 0
+#define GS_NR_ROT_MULT 1
+int gs_nonrigid_workspace_bytes(int32_t N, int32_t D, size_t* out);
+int gs_nonrigid_apply_forward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                              const float* xyz, const float* scaling, const float* rotation, float* xyz_out,
+                              float* scaling_out, float* rotation_out, float* feature, float* losses, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                               const float* scaling, const float* rotation, const float* dL_dxyz_out,
+                               const float* dL_dscaling_out, const float* dL_drotation_out, const float* dL_dfeature,
+                               const float* dL_dnr_xyz, const float* dL_dnr_scale, const float* dL_dnr_rot,
+                               float* dL_ddeltas, float* dL_dscaling, float* dL_drotation, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
  * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
