@@ -15,16 +15,16 @@
 //    (The pixel-parallel formulation needs a 64-lane reduction of nine values per list entry; DPP
 //    adds issue at half rate on gfx950 (tools/dpp_rate.hip), which made that reduction ~2/3 of the
 //    kernel.)
-//  * Entries never touch LDS: every lane gathers the record of its entry two chunks ahead, converts it
-//    at the round boundary, and at its own switch step (ring position == step mod 16) moves it into
+//  * Entries never touch LDS: every lane gathers the record of its entry two chunks ahead (its list
+//    word three), converts it at the round boundary, and at its own switch step (ring position == step mod 16) moves it into
 //    the working set.  Per-pixel constants (dL/dpixel, position, last-contributor limit) sit in LDS, one
 //    array per component, and are read at the lane's current pixel index one step ahead.
 //  * Each lane keeps TWO sets of nine gradient sums, named by the parity of the chunk they belong to:
 //    lanes that have switched in the current round add into one set, the others still into the other
 //    (the nine FMAs issued under complementary exec masks).  A set is complete for every lane one
-//    round later: it is folded over the four rings, stored by ring 0 and cleared at a round start --
-//    nothing is stored or cleared under a one-lane exec mask, where an instruction costs as much as
-//    with 64 lanes.
+//    round later: it is folded over the four rings with lane swaps (no LDS), stored by all four rings
+//    (ring r the dwords r and 4 + r of the entry's row) and cleared at a round start -- nothing is stored
+//    or cleared under a one-lane exec mask, where an instruction costs as much as with 64 lanes.
 //  * FRONT-to-back recurrence.  With g = dL/dpixel, Gtot = out_color . g (out_color already holds
 //    T_final * bg) and Rem_i = Gtot - sum_{j<=i} (c_j . g) alpha_j T_j,
 //        dL/dalpha_i = T_i (c_i . g) - Rem_i / (1 - alpha_i)
@@ -186,7 +186,15 @@ __device__ __forceinline__ void switch_entry(EntryQ& e, uint32_t lds_addr, unsig
 #ifndef BWD_MIN_WAVES
 #define BWD_MIN_WAVES 1
 #endif
+// A GUARD, without effect on the code as it stands: modes 0, 1 and 3 hold 75-76 VGPRs and run six waves per SIMD with or
+// without it (measured level).  Builds of this kernel that happened to fit 72 registers ran SEVEN
+// and were 8-10 us slower than the same code at six, so a register saved by a later change must not become a seventh
+// wave unnoticed.  (-DBWD_MIN_WAVES above six raises the cap with it.)
+#ifndef BWD_MAX_WAVES
+#define BWD_MAX_WAVES (BWD_MIN_WAVES > 6 ? BWD_MIN_WAVES : 6)
+#endif
 template <int MODE>
+__attribute__((amdgpu_waves_per_eu(BWD_MIN_WAVES, BWD_MAX_WAVES)))
 __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const float4* __restrict__ rec,
                                                         const uint2* __restrict__ ranges,
                                                         const uint32_t* __restrict__ order, int W, int H, int gx,
@@ -228,7 +236,11 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     const int lane = threadIdx.x;
     const int j = lane & (RING - 1), ring = lane / RING;  // position in the ring / which ring
     const int QX0 = tx * TILE + 8 * (q & 1), QY0 = ty * TILE + 8 * (q >> 1);
-    const int px = QX0 + (lane & 7), py = QY0 + (lane >> 3);
+    // The lane loads the pixel it STARTS with: position i of a ring starts at ring lane (16 - i) mod 16, so lane (ring, j)
+    // takes ring position pi = (16 - j) mod 16, pixel `pl` of the quadrant -- T0 and gtot0 are then where the loop wants
+    // them (until now every lane loaded pixel `lane` and the two were fetched with a __shfl each).
+    const int pi = (RING - j) & (RING - 1), pl = ring * RING + pi;
+    const int px = QX0 + (pl & 7), py = QY0 + (pl >> 3);
     const uint2 range = ranges[tile];
     const int n = (int)(range.y - range.x);
     // this wave's entries: [k0, k0 + m) of the quadrant's compacted list (the whole list when chunks = 1)
@@ -238,13 +250,14 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     const int k0 = (int)ks;
     const uint32_t ke = chunk + 1 < chunks ? ck_start[(size_t)(tile * 4 + q) * (size_t)chunks + chunk + 1] : 0xFFFFFFFFu;
     const int m = (int)min(ke, (uint32_t)m_all) - k0;
+    if (m <= 0) return;  // (a chunk holds at least one entry: the gathers below read list word min(k, m - 1))
     const uint32_t qbase = 4u * range.x + (uint32_t)q * (uint32_t)n + (uint32_t)k0;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float gtot0, T0 = 1.0f;  // Gtot of pixel `lane` (what of it is not composited before entry k0), its transmittance there
+    float gtot0, T0 = 1.0f;  // Gtot of pixel `pl` (what of it is not composited before entry k0), its transmittance there
     {
         // (g0, g1, g2, Gtot) and (x, y, lim): the pixel at position i of its ring meets compacted entry k at
         // step s = k + i, and the pair counts only while k < (its last contributor) <=> s < lim = ncon + i
-        float4 c0 = zero4, c1 = make_float4((float)px, (float)py, __uint_as_float((uint32_t)j), 0.f);
+        float4 c0 = zero4, c1 = make_float4((float)px, (float)py, __uint_as_float((uint32_t)pi), 0.f);
         float3 h = make_float3(0.f, 0.f, 0.f);  // (SECOND) dL/dpixel of the second image
         if (px < W && py < H) {
             const size_t HW = (size_t)H * W;
@@ -263,7 +276,7 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
             }
             c0 = make_float4(g0, g1, g2, o0 * g0 + o1 * g1 + o2 * g2);
             const uint32_t nc = ncon_c[pid];
-            c1.z = __uint_as_float((nc > (uint32_t)k0 ? nc - (uint32_t)k0 : 0u) + (uint32_t)j);
+            c1.z = __uint_as_float((nc > (uint32_t)k0 ? nc - (uint32_t)k0 : 0u) + (uint32_t)pi);
             // An image whose colours are all ONE -- the opacity channel o = (1 - Tf) + Tf bg, or a second render with
             // colours (1, 1, 1) -- needs nothing in the loop: its (c . g) is the same g4 for every entry, and with
             // sum_{j <= i} alpha_j T_j = 1 - T_{i+1} its share of dL/dalpha_i = T_i g4 - Rem_i / (1 - alpha_i) collapses to
@@ -281,7 +294,7 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
             }
             if (chunk > 0) {
                 // the forward's state before entry k0: T, and the colour composited so far (the opacity channel's is 1 - T)
-                const size_t ci = ((size_t)(tile * 4 + q) * (size_t)(chunks - 1) + (size_t)(chunk - 1)) * 64 + lane;
+                const size_t ci = ((size_t)(tile * 4 + q) * (size_t)(chunks - 1) + (size_t)(chunk - 1)) * 64 + pl;
                 const float4 ck = ckpt[ci];
                 T0 = ck.x;
                 c0.w -= ck.y * g0 + ck.z * g1 + ck.w * g2;
@@ -291,7 +304,7 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
                 }
             }
         }
-        const int slot = ring * RING_STRIDE + j;
+        const int slot = ring * RING_STRIDE + pi;
         pix[0][slot] = pix[0][slot + RING] = make_float2(c0.x, c0.y);
         pix[1][slot] = pix[1][slot + RING] = make_float2(c0.z, c1.x);
         pix[2][slot] = pix[2][slot + RING] = make_float2(c1.y, c1.z);
@@ -316,23 +329,31 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
             e[2] = bwd_f4{p2.x, q2.x, q2.y, q2.z};
         }
     };
-    auto gather = [&](int k, float4& p0, float4& p1, float4& p2) {
-        if (k < m) {
-            const uint32_t id = qlist[qbase + k];
-            p0 = rec[(size_t)id * 3];
-            p1 = rec[(size_t)id * 3 + 1];
-            p2 = rec[(size_t)id * 3 + 2];
-            if (SECOND) q2 = make_float3(second.colors[(size_t)id * 3], second.colors[(size_t)id * 3 + 1], second.colors[(size_t)id * 3 + 2]);
-        }
+    // The gathers are UNCONDITIONAL, at list word min(k, m - 1), and the list word is read a round before the record it
+    // names.  (Until now `if (k < m) { id = qlist[..]; p = rec[id] }`: the compiler merged the old and the new record inside
+    // that branch -- register moves behind an `s_waitcnt vmcnt(0)` -- so every round start waited for two dependent memory
+    // round trips it had meant to leave in flight.  A lane past the end of the list holds a copy of the last entry: no
+    // pixel meets it before its own limit `lim`, and its sums are never stored.)
+    uint32_t id_ahead = 0;  // the list word of this lane's entry one chunk beyond the gathered one
+    auto gather_id = [&](int k) { id_ahead = qlist[qbase + min(k, m - 1)]; };
+    auto gather = [&](float4& p0, float4& p1, float4& p2) {  // the record `id_ahead` names
+        const uint32_t id = id_ahead;
+        p0 = rec[(size_t)id * 3];
+        p1 = rec[(size_t)id * 3 + 1];
+        p2 = rec[(size_t)id * 3 + 2];
+        if (SECOND) q2 = make_float3(second.colors[(size_t)id * 3], second.colors[(size_t)id * 3 + 1], second.colors[(size_t)id * 3 + 2]);
     };
 
     float4 p0 = zero4, p1 = zero4, p2 = zero4;
     EntryQ cur;  // the entry this lane works on (none yet: alpha = 0)
     cur.q0 = cur.q1 = cur.q2 = bwd_f4{0.f, 0.f, 0.f, 0.f};
     uint32_t row_staged = 0;  // gradient row of this lane's entry in the chunk staged last
-    gather(j, p0, p1, p2);              // (the four rings hold the same entries)
+    gather_id(j);
+    gather(p0, p1, p2);                 // (the four rings hold the same entries)
+    gather_id(RING + j);
     stage(p0, p1, p2, 0, row_staged);   // chunk 0, taken by position t of every ring at step t
-    gather(RING + j, p0, p1, p2);       // chunk 1 in flight during round 0
+    gather(p0, p1, p2);                 // chunk 1 in flight during round 0
+    gather_id(2 * RING + j);            // ... and the list word of chunk 2
     __syncthreads();
     // LDS address of this lane's entry in the two slots
     const uint32_t ent_addr0 = (uint32_t)(uintptr_t)&ent[0][j][0], ent_addr1 = (uint32_t)(uintptr_t)&ent[1][j][0];
@@ -340,7 +361,7 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     // Two accumulator sets, named by the PARITY of the chunk they belong to: during round R the lanes
     // that have already taken their entry of chunk R (lane <= t) add into set R & 1, the others still
     // add into the set of chunk R - 1.  A set is therefore complete for ALL lanes when round R + 1 ends
-    // ... i.e. it is stored (three full-wave stores) and cleared at the start of round R + 2, instead
+    // ... i.e. it is stored (two full-wave dword stores and ring 0's ninth word) and cleared at the start of round R + 2, instead
     // of every lane storing / clearing its own sums at its own switch step under a one-lane exec mask
     // (where every instruction costs as much as a full-wave one).
     float accA[9], accB[9];
@@ -348,51 +369,88 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     for (int c9 = 0; c9 < 9; c9++) accA[c9] = accB[c9] = 0.f;
     uint32_t rowA = 0, rowB = 0;  // gradient rows of the entries the sets belong to
     // index into pix[c][] of the pixel at this lane: ring base + (s - j) mod 16, + 16 within a round
-    uint32_t pidx = (uint32_t)(ring * RING_STRIDE + ((RING - j) & (RING - 1)));
+    uint32_t pidx = (uint32_t)(ring * RING_STRIDE + pi);
     float2 pc[NP2];
 #pragma unroll
     for (int c6 = 0; c6 < NP2; c6++) pc[c6] = pix[c6][pidx];
     // state of the pixel currently at this lane: transmittance and the part of Gtot not yet composited
-    // (position i of a ring starts at ring lane (16 - i) mod 16; fetch its Gtot from the lane that loaded it)
-    float T = __shfl(T0, ring * RING + ((RING - j) & (RING - 1)), 64);
-    float Rem = __shfl(gtot0, ring * RING + ((RING - j) & (RING - 1)), 64);
+    // (the lane loaded the pixel it starts with)
+    float T = T0, Rem = gtot0;
 
-    // A finished entry's nine RAW sums go to its row in HBM.  What is constant per Gaussian -- opacity,
-    // the conic combination of the two first moments, the -1/2 and 1/log2(e) factors -- is applied once
-    // per Gaussian by segment_reduce_kernel.
-    auto write_row = [&](size_t row, const float* a) {
+    // The four rings hold partial sums of the same entries.  FOLD, without the LDS unit (until now 18 ds_bpermute per fold):
+    // v_permlane16_swap on (p, q) exchanges the odd rows of p with the even rows of q, so p + q has the rows
+    // [A0+A1, B0+B1, A2+A3, B2+B3] of two sums A, B; v_permlane32_swap on two such registers exchanges the upper half of
+    // one with the lower half of the other, and their sum has the rows [A, B, C, D], A = (A0 + A1) + (A2 + A3) -- the
+    // association the xor 16, xor 32 ladder gave ring 0, so the stored bits are what they were.  Row r of f[0] is sum r, of
+    // f[1] sum 4 + r; f[2] is sum 8 in every row.
+    // (One asm statement, the sums folded in place: with the two builtins the register allocator no longer kept the
+    // accumulator sets in fixed registers across the rounds -- 94 VGPRs and moves inside the step loop.  `s_nop 1`: a swap
+    // must not read a register a VALU instruction wrote within the last two wait states; inside the statement every swap's
+    // operands are at least two instructions old.)
+    auto fold_rings = [&](float (&a)[9], float (&f)[3]) {
+        float t;
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_permlane16_swap_b32 %[a0], %[a1]\n\t"
+            "v_permlane16_swap_b32 %[a2], %[a3]\n\t"
+            "v_permlane16_swap_b32 %[a4], %[a5]\n\t"
+            "v_permlane16_swap_b32 %[a6], %[a7]\n\t"
+            "v_mov_b32 %[t], %[a8]\n\t"
+            "v_add_f32 %[a0], %[a0], %[a1]\n\t"
+            "v_add_f32 %[a2], %[a2], %[a3]\n\t"
+            "v_add_f32 %[a4], %[a4], %[a5]\n\t"
+            "v_add_f32 %[a6], %[a6], %[a7]\n\t"
+            "v_permlane16_swap_b32 %[a8], %[t]\n\t"
+            "v_permlane32_swap_b32 %[a0], %[a2]\n\t"
+            "v_permlane32_swap_b32 %[a4], %[a6]\n\t"
+            "v_add_f32 %[a8], %[a8], %[t]\n\t"
+            "v_add_f32 %[a0], %[a0], %[a2]\n\t"
+            "v_add_f32 %[a4], %[a4], %[a6]\n\t"
+            "v_mov_b32 %[t], %[a8]\n\t"
+            "s_nop 1\n\t"
+            "v_permlane32_swap_b32 %[a8], %[t]\n\t"
+            "v_add_f32 %[a8], %[a8], %[t]"
+            : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [a4] "+v"(a[4]), [a5] "+v"(a[5]),
+              [a6] "+v"(a[6]), [a7] "+v"(a[7]), [a8] "+v"(a[8]), [t] "=&v"(t));
+        f[0] = a[0];
+        f[1] = a[4];
+        f[2] = a[8];
+    };
+    // A finished entry's nine RAW sums go to its row in HBM: ring r stores dwords r and 4 + r of the entry's 32-byte row (two
+    // full-wave dword stores: the four rings' lanes of an entry fill 16 contiguous bytes each), ring 0 the ninth word.  What
+    // is constant per Gaussian -- opacity, the conic combination of the two first moments, the -1/2 and 1/log2(e) factors --
+    // is applied once per Gaussian by segment_reduce_kernel.
+    float* const qrow_words = reinterpret_cast<float*>(qrows);
+    auto write_row = [&](size_t row, const float (&f)[3]) {
         // (plain stores: the rows are read back by segment_reduce_kernel while much of them is still in the L2 / MALL --
         // streaming "nt" stores made the frame 0.15 ms slower)
-        qrows[row * 2] = make_float4(a[0], a[1], a[2], a[3]);
-        qrows[row * 2 + 1] = make_float4(a[4], a[5], a[6], a[7]);
-        q8[row] = __float_as_uint(a[8]);  // the ninth sum doubles as the "row written" mark
+        qrow_words[row * 8 + ring] = f[0];
+        qrow_words[row * 8 + ring + 4] = f[1];
+        if (ring == 0) q8[row] = __float_as_uint(f[2]);  // the ninth sum doubles as the "row written" mark
     };
 
     // An entry k lives at position k mod 16 of every ring for the steps k .. k+15; the loop runs
     // s = 0 .. m+14, so every entry has seen all its pixels when the loop ends.
     const int total = m + RING - 1;
-    // the four rings hold partial sums of the same entries: fold them (every lane ends with the total)
-    auto fold_rings = [&](float (&a)[9]) {
-#pragma unroll
-        for (int c9 = 0; c9 < 9; c9++) {
-            a[c9] += __shfl_xor(a[c9], 16, 64);
-            a[c9] += __shfl_xor(a[c9], 32, 64);
-        }
-    };
     auto run_round = [&](const int s0, float (&X)[9], uint32_t& rowX, float (&Y)[9]) {
         // Round start (round R = s0 / 16).  X holds the finished sums of chunk R - 2: store them.  The lanes switch to
         // chunk R during this round (staged one round ago): its row is the one noted then.  The chunk that was in flight
         // (R + 1) is converted and staged for the next round; the chunk after it goes in flight.
-        if (s0 >= 2 * RING) {
-            fold_rings(X);
-            if (ring == 0) write_row(rowX, X);
-        }
+        const uint32_t row_done = rowX;
         rowX = row_staged;
         const uint32_t ea = (s0 & RING) ? ent_addr1 : ent_addr0;  // this round's chunk: slot R & 1
         // position 0 of every ring takes its entry now (the other positions at the end of the step before theirs)
         switch_entry<SECOND>(cur, ea, 0ull, 0x0001000100010001ull);
         stage(p0, p1, p2, s0 / RING + 1, row_staged);  // (behind the read above: slot (R + 1) & 1 held chunk R - 1)
-        gather(s0 + 2 * RING + j, p0, p1, p2);
+        gather(p0, p1, p2);                            // chunk R + 2
+        gather_id(s0 + 3 * RING + j);
+        // ... and the stores BEHIND the round's loads: the counter the loads are waited for with counts the stores too, in
+        // order, so stores issued in front of them were waited for with them at the next round start
+        if (s0 >= 2 * RING) {
+            float f[3];
+            fold_rings(X, f);
+            write_row(row_done, f);
+        }
         if (s0 > 0) pidx -= (uint32_t)RING;
 #pragma unroll
         for (int c9 = 0; c9 < 9; c9++) X[c9] = 0.f;
@@ -455,12 +513,11 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
         const int last_round = (total - 1) / RING;
         const bool odd = last_round & 1;
         const int k_new = RING * last_round + j, k_old = k_new - RING;
-        fold_rings(accA);
-        fold_rings(accB);
-        if (ring == 0) {
-            if (k_new <= m - 1) write_row(odd ? rowB : rowA, odd ? accB : accA);
-            if (last_round >= 1 && k_old <= m - 1) write_row(odd ? rowA : rowB, odd ? accA : accB);
-        }
+        float fA[3], fB[3];
+        fold_rings(accA, fA);
+        fold_rings(accB, fB);
+        if (k_new <= m - 1) write_row(odd ? rowB : rowA, odd ? fB : fA);
+        if (last_round >= 1 && k_old <= m - 1) write_row(odd ? rowA : rowB, odd ? fA : fB);
     }
 }
 
