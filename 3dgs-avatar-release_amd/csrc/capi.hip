@@ -736,6 +736,56 @@ int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, d
     return launch_adam(n_tensors, tensors, beta1, beta2, eps, step, (hipStream_t)stream);
 }
 
+// ---- the converter's optimizer step (optim.hip): every argument check comes before the first HIP call
+#define GS_OPTIM_MAX_N ((int64_t)1 << 41)  // chunks of 2048 elements are counted in an int
+static int grad_tensors_ok(int32_t n_tensors, const GsGradTensor* tensors) {
+    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n < 0 || (tensors[k].n > 0 && !tensors[k].grad)) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
+    return GS_OK;
+}
+int gs_grad_norm_workspace_bytes(int32_t n_tensors, const GsGradTensor* tensors, size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    *out = grad_norm_workspace_bytes(n_tensors, tensors);
+    return GS_OK;
+}
+int gs_grad_norm(int32_t n_tensors, const GsGradTensor* tensors, float max_norm, float* out, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    if (!out || !workspace || !(max_norm >= 0.f)) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    if (workspace_bytes < grad_norm_workspace_bytes(n_tensors, tensors)) return GS_E_WORKSPACE;
+    if (n_tensors == 0) return GS_OK;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_grad_norm(n_tensors, tensors, max_norm, out, (float*)workspace, (hipStream_t)stream);
+}
+int gs_grad_scale(int32_t n_tensors, const GsGradTensor* tensors, const float* clip_coef, void* stream) {
+    if (!clip_coef) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    if (n_tensors == 0) return GS_OK;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_grad_scale(n_tensors, tensors, clip_coef, (hipStream_t)stream);
+}
+int gs_adam_step_ex(int32_t n_tensors, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
+                    const float* clip_coef, void* stream) {
+    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
+    bool host_step = false;
+    for (int k = 0; k < n_tensors; k++) {
+        const GsAdamTensorEx& t = tensors[k];
+        if (t.n < 0 || (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) return GS_E_BAD_ARG;
+        if (!t.step) host_step = true;
+    }
+    if (host_step && step < 1) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
+    if (n_tensors == 0) return GS_OK;
+    // (a host step number under capture: a replay would repeat the captured step's bias correction)
+    GS_CAPTURE_OK_IF(stream, !host_step);
+    return launch_adam_ex(n_tensors, tensors, beta1, beta2, eps, host_step ? step : 0, clip_coef, (hipStream_t)stream);
+}
+
 // ---- densification cycle (densify.hip).  N < 2^30: the map packs a source index and a two-bit slot into 32 bits, and
 // N' <= 2 N stays an int32
 #define GS_DENSIFY_MAX_N (1 << 30)

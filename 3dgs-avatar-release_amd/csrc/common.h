@@ -646,6 +646,12 @@ int launch_tile_lists(const uint4* ranklist, const uint32_t* chunk_pairs, uint32
 int launch_densify_stats(int N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
                          float* xyz_gradient_accum, float* denom, hipStream_t s);
 int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s);
+// the converter's optimizer step (optim.hip): deterministic global gradient norm, in-place scale, extended Adam
+size_t grad_norm_workspace_bytes(int n, const GsGradTensor* tensors);
+int launch_grad_norm(int n, const GsGradTensor* tensors, float max_norm, float* out, float* workspace, hipStream_t s);
+int launch_grad_scale(int n, const GsGradTensor* tensors, const float* clip_coef, hipStream_t s);
+int launch_adam_ex(int n, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
+                   const float* clip_coef, hipStream_t s);
 // densification cycle (densify.hip)
 size_t densify_workspace_bytes(int N);
 int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_host, hipStream_t s);

@@ -48,7 +48,8 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_skinning_backward",
            "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward",
            "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
-           "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward"]
+           "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
+           "gs_grad_norm_workspace_bytes", "gs_grad_norm", "gs_grad_scale", "gs_adam_step_ex"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
 GS_E_CAPTURE = -6
@@ -63,6 +64,18 @@ GS_BIN_POINT_LIST, GS_BIN_QLIST, GS_BIN_FIELDS = range(3)
 class GsAdamTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsAdamTensor
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("n", c_int64), ("lr", c_float)]
+
+
+GS_OPTIM_MAX_TENSORS, GS_GRAD_NORM_BATCH, GS_ADAM_EX_BATCH, GS_ADAM_STEP_BATCH = 4096, 192, 48, 384  # include/gsplat_mi355.h
+
+
+class GsGradTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsGradTensor
+    _fields_ = [("grad", c_void_p), ("n", c_int64)]
+
+
+class GsAdamTensorEx(ctypes.Structure):  # include/gsplat_mi355.h: GsAdamTensorEx
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("n", c_int64), ("lr", c_float), ("weight_decay", c_float), ("step", c_void_p), ("lr_dev", c_void_p)]
 
 
 GS_DENSIFY_MAX_TENSORS = 24  # include/gsplat_mi355.h: GS_DENSIFY_*
@@ -179,6 +192,11 @@ def load():
         L.knn_points.argtypes = [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_densify_stats.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_adam_step.argtypes = [c_int32, POINTER(GsAdamTensor), c_double, c_double, c_double, c_int64, c_void_p]
+        L.gs_grad_norm_workspace_bytes.argtypes = [c_int32, POINTER(GsGradTensor), POINTER(c_size_t)]
+        L.gs_grad_norm.argtypes = [c_int32, POINTER(GsGradTensor), c_float, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_grad_scale.argtypes = [c_int32, POINTER(GsGradTensor), c_void_p, c_void_p]
+        L.gs_adam_step_ex.argtypes = [c_int32, POINTER(GsAdamTensorEx), c_double, c_double, c_double, c_int64, c_void_p,
+                                      c_void_p]
         L.gs_densify_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
         L.gs_densify_plan.argtypes = [POINTER(GsDensifyPlan), c_void_p, c_size_t, c_void_p, c_void_p]
         L.gs_densify_apply.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, POINTER(GsDensifyTensor), c_void_p,

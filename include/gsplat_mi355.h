@@ -50,10 +50,11 @@ extern "C" {
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
  *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward,
- *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward
+ *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward,
+ *   gs_grad_norm, gs_grad_scale, gs_adam_step_ex (every tensor with a device-resident step number)
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
- * step's bias correction), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
+ * step's bias correction; gs_adam_step_ex likewise for a tensor without a device step), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
  * anything in debug mode. */
 
 /* Arguments of one rasterizer call: the fields of GaussianRasterizationSettings
@@ -318,6 +319,59 @@ int gs_densify_stats(int32_t N, const int32_t* radii, const float* viewspace_gra
                      float* xyz_gradient_accum, float* denom, void* stream);
 int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step,
                  void* stream);
+
+/* ---- the converter's optimizer step (models/gaussian_converter.py:22-39,61-67): clip_grad_norm_ + torch.optim.Adam
+ * with per-group weight decay over ~130 parameter tensors, in a handful of launches, with no host synchronisation and a
+ * step number that may live on the device (so that the step can be captured into a hipGraph).
+ *
+ * gs_grad_norm: the global L2 norm of all `tensors` (fp32, contiguous; any alignment).  Every workgroup sums the squares
+ *   of one fixed chunk of one tensor into a partial in `workspace` (gs_grad_norm_workspace_bytes of the SAME tensor
+ *   list); one workgroup adds the partials in a fixed order.  No atomics: the same gradients give the same bits on
+ *   every run.  out[0] = total_norm, out[1] = clip_coef = max_norm / (total_norm + 1e-6) limited to 1 the way
+ *   torch.clamp(max=1.0) limits it: a NaN norm gives a NaN coefficient (and an infinite one gives 0).
+ * gs_grad_scale: grad *= *clip_coef in place, for the stand-alone clip_grad_norm_.
+ * gs_adam_step_ex: gs_adam_step's arithmetic on the effective gradient  *clip_coef * grad + weight_decay * param
+ *   (torch's Adam, not AdamW; clip_coef == NULL means 1).  THE GRADIENTS ARE NOT REWRITTEN: after the call they still hold
+ *   the unclipped values (torch.nn.utils.clip_grad_norm_ scales them in place; gs_grad_scale does that where it is wanted).
+ *   Per tensor: `step` == NULL takes the call's host `step` (>= 1); otherwise `step` points to the tensor's device-resident
+ *   fp32 step number, which the call increments by one (in a launch of its own, in front of the update; also for a tensor
+ *   with n == 0, whose update is skipped) and then reads: every workgroup forms 1 - beta1^step and sqrt(1 - beta2^step) in
+ *   double and rounds them to fp32 once, as the host does for a host step.  `lr_dev` == NULL takes `lr`; otherwise the
+ *   learning rate is read from that device fp32 scalar (torch's convention for capturable optimizers: a scheduler's
+ *   change is seen by a replayed graph).
+ * The tensor tables travel to the kernels by value in batches of GS_GRAD_NORM_BATCH / GS_ADAM_EX_BATCH (kernel
+ * arguments are limited to 4 KB); the entry points take up to GS_OPTIM_MAX_TENSORS tensors and loop over the batches.
+ * GS_E_BAD_ARG (before any HIP call): a count outside 0..GS_OPTIM_MAX_TENSORS, a NULL table with a positive count, a
+ * negative n, a NULL pointer of a tensor with n > 0, NULL out / workspace / clip_coef (gs_grad_scale), a negative or NaN
+ * max_norm, step < 1 while some tensor has no device step.  GS_E_TOO_LARGE: a tensor of 2^41 elements or more.
+ * GS_E_WORKSPACE: the workspace is smaller than gs_grad_norm_workspace_bytes says.  Zero tensors: GS_OK with nothing
+ * enqueued (`out` is then left as it is; tensors that are all empty give total_norm = 0, clip_coef = 1).  All four are capture-safe when every step number is device-resident; gs_adam_step_ex with
+ * a host step number on a capturing stream answers GS_E_CAPTURE with nothing enqueued. ---- */
+#define GS_OPTIM_MAX_TENSORS 4096
+#define GS_GRAD_NORM_BATCH 192  /* tensors per launch of the norm / scale kernels  */
+#define GS_ADAM_EX_BATCH 48     /* tensors per launch of the extended Adam update   */
+#define GS_ADAM_STEP_BATCH 384  /* device step numbers per launch of the begin-step pass */
+typedef struct GsGradTensor {
+    float* grad;
+    int64_t n;   /* elements */
+} GsGradTensor;
+typedef struct GsAdamTensorEx {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;            /* elements */
+    float lr;             /* used when lr_dev == NULL */
+    float weight_decay;
+    float* step;          /* device fp32 step number, incremented by the call; NULL: the call's host `step` */
+    const float* lr_dev;  /* device fp32 learning rate; NULL: `lr` */
+} GsAdamTensorEx;
+int gs_grad_norm_workspace_bytes(int32_t n_tensors, const GsGradTensor* tensors, size_t* out);
+int gs_grad_norm(int32_t n_tensors, const GsGradTensor* tensors, float max_norm, float* out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int gs_grad_scale(int32_t n_tensors, const GsGradTensor* tensors, const float* clip_coef, void* stream);
+int gs_adam_step_ex(int32_t n_tensors, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
+                    const float* clip_coef, void* stream);
 
 /* ---- densification cycle (scene/gaussian_model.py:263-266,311-462; train.py:217-227): clone, split and prune with the
  * Adam-state surgery, and reset_opacity.  The full semantics are spelled out at the top of csrc/densify.hip.
