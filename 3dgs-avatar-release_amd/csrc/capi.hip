@@ -1098,6 +1098,73 @@ int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32
                                           dL_ddeltas, dL_dscaling, dL_drotation, (hipStream_t)stream);
 }
 
+// ---- the input of the ColorMLP texture (texture.hip)
+static int texture_validate(const GsTextureArgs* a) {
+    if (!a || a->N < 0 || a->sh_degree < 0 || a->sh_degree > 4 || a->n_before < 0 || a->n_before > GS_TEXTURE_MAX_BEFORE ||
+        a->n_after < 0 || a->n_after > GS_TEXTURE_MAX_AFTER || a->latent_dim < 0 || a->latent_dim > GS_TEXTURE_MAX_D)
+        return GS_E_BAD_ARG;
+    int64_t sum = (a->sh_degree + 1) * (a->sh_degree + 1) - 1 + a->latent_dim;
+    for (int b = 0; b < a->n_before; b++) {
+        if (a->before_w[b] < 1 || a->before_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
+        sum += a->before_w[b];
+    }
+    for (int b = 0; b < a->n_after; b++) {
+        if (a->after_w[b] < 1 || a->after_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
+        sum += a->after_w[b];
+    }
+    if (a->D < 1 || a->D > GS_TEXTURE_MAX_D || sum != a->D) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+// what the view direction is made of (sh_degree > 0)
+static bool texture_dir_ok(const GsTextureArgs* a) {
+    if (!pose_req(a->xyz) || !pose_req(a->campos) || !pose_a4(a->fwd_transform)) return false;
+    return !a->fwd_transform || (a->rot_row >= 3 && a->rot_stride >= 2 * (int64_t)a->rot_row + 3);
+}
+int gs_texture_workspace_bytes(int32_t N, int32_t D, int32_t latent_dim, size_t* out) {
+    if (!out || N < 0 || D < 1 || D > GS_TEXTURE_MAX_D || latent_dim < 0 || latent_dim > D) return GS_E_BAD_ARG;
+    *out = texture_workspace_bytes(N, D, latent_dim);
+    return GS_OK;
+}
+int gs_texture_input_forward(const GsTextureArgs* a, float* inp, void* stream) {
+    if (const int rc = texture_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!inp || !nr_a16(inp)) return GS_E_BAD_ARG;
+    for (int b = 0; b < a->n_before; b++)
+        if (!a->before[b] || !nr_a16(a->before[b])) return GS_E_BAD_ARG;
+    for (int b = 0; b < a->n_after; b++)
+        if (!a->after[b] || !nr_a16(a->after[b])) return GS_E_BAD_ARG;
+    if (a->latent_dim > 0 && !pose_req(a->latent)) return GS_E_BAD_ARG;
+    if (a->sh_degree > 0 && !texture_dir_ok(a)) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_texture_input_forward(a, inp, (hipStream_t)stream);
+}
+int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, float* const* dL_dbefore, float* const* dL_dafter,
+                              float* dL_dxyz, float* dL_dlatent, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = texture_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!dL_dinp || !nr_a16(dL_dinp)) return GS_E_BAD_ARG;
+    TxGrads gr = {};
+    bool any = dL_dxyz || dL_dlatent;
+    for (int b = 0; b < a->n_before; b++) {
+        gr.before[b] = dL_dbefore ? dL_dbefore[b] : nullptr;
+        if (!nr_a16(gr.before[b])) return GS_E_BAD_ARG;
+        any = any || gr.before[b];
+    }
+    for (int b = 0; b < a->n_after; b++) {
+        gr.after[b] = dL_dafter ? dL_dafter[b] : nullptr;
+        if (!nr_a16(gr.after[b])) return GS_E_BAD_ARG;
+        any = any || gr.after[b];
+    }
+    if (dL_dxyz && (a->sh_degree == 0 || !pose_a4(dL_dxyz) || !texture_dir_ok(a))) return GS_E_BAD_ARG;
+    if (dL_dlatent) {
+        if (a->latent_dim == 0 || !pose_a4(dL_dlatent) || !workspace || !pose_a4(workspace)) return GS_E_BAD_ARG;
+        if (workspace_bytes < texture_workspace_bytes(a->N, a->D, a->latent_dim)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!any) return GS_OK;
+    return launch_texture_input_backward(a, dL_dinp, gr, dL_dxyz, dL_dlatent, workspace, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

@@ -706,6 +706,15 @@ int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const flo
                                    const float* g_xyz, const float* g_scal, const float* g_rot, const float* g_feat,
                                    const float* g_nrx, const float* g_nrs, const float* g_nrr, float* ddeltas, float* dscal,
                                    float* drot, hipStream_t s);
+// the input of the ColorMLP texture (texture.hip; the spec is at its top).  TxGrads: the block gradients' addresses, by value
+struct TxGrads {
+    float* before[GS_TEXTURE_MAX_BEFORE];
+    float* after[GS_TEXTURE_MAX_AFTER];
+};
+size_t texture_workspace_bytes(int N, int D, int latent_dim);
+int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s);
+int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const TxGrads& grads, float* dxyz, float* dlatent,
+                                  void* workspace, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

@@ -187,6 +187,33 @@ __device__ __forceinline__ float3 sh_to_rgb(int deg, const float3 mean, const fl
     return sh_eval_dir(deg, dx / len, dy / len, dz / len, sh, clamped);
 }
 
+// ---- the view direction of the texture modules (prepass.hip's sh2rgb, texture.hip)
+struct Mat3 { float m[9]; };  // row-major, by value (the optional view-noise matrix)
+
+// direction of texture.py:23-35: d = xyz - campos; cano: d = R_fwd^T d; noise: d = d @ noise; unit = d / (|d| + 1e-12).
+// R_fwd (NULL = none): row i's rotation starts at R_fwd + ms i, its rows rs floats apart (contiguous (N, 3, 3): 9 and 3;
+// the corner of (N, 4, 4) transforms read in place: 16 and 4)
+__device__ __forceinline__ void view_dir(const float* __restrict__ xyz, const float* __restrict__ campos,
+                                         const float* __restrict__ R_fwd, int ms, int rs, int use_noise, const Mat3& noise, int i,
+                                         float d[3], float* len) {
+    float v[3] = {xyz[3 * (size_t)i] - campos[0], xyz[3 * (size_t)i + 1] - campos[1], xyz[3 * (size_t)i + 2] - campos[2]};
+    if (R_fwd) {
+        const float* R = R_fwd + ms * (size_t)i;
+        const float w[3] = {R[0] * v[0] + R[rs] * v[1] + R[2 * rs] * v[2], R[1] * v[0] + R[rs + 1] * v[1] + R[2 * rs + 1] * v[2],
+                            R[2] * v[0] + R[rs + 2] * v[1] + R[2 * rs + 2] * v[2]};  // R^T v
+        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
+    }
+    if (use_noise) {
+        const float w[3] = {v[0] * noise.m[0] + v[1] * noise.m[3] + v[2] * noise.m[6],
+                            v[0] * noise.m[1] + v[1] * noise.m[4] + v[2] * noise.m[7],
+                            v[0] * noise.m[2] + v[1] * noise.m[5] + v[2] * noise.m[8]};  // v @ noise
+        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
+    }
+    const float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
+    *len = l;
+}
+
 // ---- SH tiles: the (M,3) coefficient block of Gaussian i is 3M contiguous floats, so a thread-per-
 // Gaussian kernel reading (or writing) it directly touches a different cache line per lane on every
 // access.  These helpers move a whole workgroup's rows between HBM and LDS with coalesced dword

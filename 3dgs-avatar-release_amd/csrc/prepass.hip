@@ -100,30 +100,6 @@ __global__ __launch_bounds__(256) void build_cov_bwd_kernel(int N, const float* 
     }
 }
 
-struct Mat3 { float m[9]; };  // row-major, by value (the optional view-noise matrix)
-
-// direction of texture.py:23-35: d = xyz - campos; cano: d = R_fwd^T d; noise: d = d @ noise; unit = d / (|d| + 1e-12)
-__device__ __forceinline__ void view_dir(const float* __restrict__ xyz, const float* __restrict__ campos,
-                                         const float* __restrict__ R_fwd, int use_noise, const Mat3& noise, int i, float d[3],
-                                         float* len) {
-    float v[3] = {xyz[3 * (size_t)i] - campos[0], xyz[3 * (size_t)i + 1] - campos[1], xyz[3 * (size_t)i + 2] - campos[2]};
-    if (R_fwd) {
-        const float* R = R_fwd + 9 * (size_t)i;
-        const float w[3] = {R[0] * v[0] + R[3] * v[1] + R[6] * v[2], R[1] * v[0] + R[4] * v[1] + R[7] * v[2],
-                            R[2] * v[0] + R[5] * v[1] + R[8] * v[2]};  // R^T v
-        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
-    }
-    if (use_noise) {
-        const float w[3] = {v[0] * noise.m[0] + v[1] * noise.m[3] + v[2] * noise.m[6],
-                            v[0] * noise.m[1] + v[1] * noise.m[4] + v[2] * noise.m[7],
-                            v[0] * noise.m[2] + v[1] * noise.m[5] + v[2] * noise.m[8]};  // v @ noise
-        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
-    }
-    const float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
-    *len = l;
-}
-
 __device__ __forceinline__ void load_sh48(const float* __restrict__ g, int M, float* l, bool vec) {
     if (vec) {
         const float4* g4 = reinterpret_cast<const float4*>(g);
@@ -145,7 +121,7 @@ __global__ __launch_bounds__(256) void sh2rgb_kernel(int N, int deg, int M, cons
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     float d[3], len;
-    view_dir(xyz, campos, R_fwd, use_noise, noise, i, d, &len);
+    view_dir(xyz, campos, R_fwd, 9, 3, use_noise, noise, i, d, &len);
     const float inv = 1.0f / (len + 1e-12f);
     float l[48];
     load_sh48(shs + (size_t)i * M * 3, M, l, M == 16 && ((uintptr_t)shs & 15u) == 0);
@@ -166,7 +142,7 @@ __global__ __launch_bounds__(256) void sh2rgb_bwd_kernel(int N, int deg, int M, 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     float d[3], len;
-    view_dir(xyz, campos, R_fwd, use_noise, noise, i, d, &len);
+    view_dir(xyz, campos, R_fwd, 9, 3, use_noise, noise, i, d, &len);
     const float inv = 1.0f / (len + 1e-12f);
     const float x = d[0] * inv, y = d[1] * inv, z = d[2] * inv;
     const bool vec = M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dshs) & 15u) == 0;

@@ -49,6 +49,7 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward",
            "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
            "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
+           "gs_texture_workspace_bytes", "gs_texture_input_forward", "gs_texture_input_backward",
            "gs_grad_norm_workspace_bytes", "gs_grad_norm", "gs_grad_scale", "gs_adam_step_ex"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
@@ -125,6 +126,17 @@ class GsPoseEncArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsPoseEncArgs
     _fields_ = [("d", c_int32), ("parents", c_int32 * GS_POSE_ENC_JOINTS)] + [
         (n, c_void_p) for n in ("rots", "Jtrs", "W0", "b0")] + [
         (n, c_void_p * GS_POSE_ENC_JOINTS) for n in ("W1", "b1", "W2", "b2")]
+
+
+GS_TEXTURE_MAX_D, GS_TEXTURE_MAX_BEFORE, GS_TEXTURE_MAX_AFTER = 512, 6, 2  # include/gsplat_mi355.h
+
+
+class GsTextureArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsTextureArgs
+    _fields_ = [("N", c_int32), ("D", c_int32), ("sh_degree", c_int32), ("n_before", c_int32), ("n_after", c_int32),
+                ("before_w", c_int32 * GS_TEXTURE_MAX_BEFORE), ("after_w", c_int32 * GS_TEXTURE_MAX_AFTER),
+                ("latent_dim", c_int32), ("rot_stride", c_int32), ("rot_row", c_int32), ("use_noise", c_int32),
+                ("noise", c_float * 9), ("before", c_void_p * GS_TEXTURE_MAX_BEFORE), ("after", c_void_p * GS_TEXTURE_MAX_AFTER),
+                ("xyz", c_void_p), ("campos", c_void_p), ("fwd_transform", c_void_p), ("latent", c_void_p)]
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -227,6 +239,10 @@ def load():
         L.gs_nonrigid_workspace_bytes.argtypes = [c_int32, c_int32, POINTER(c_size_t)]
         L.gs_nonrigid_apply_forward.argtypes = [c_int32] * 4 + [c_void_p] * 10 + [c_size_t, c_void_p]
         L.gs_nonrigid_apply_backward.argtypes = [c_int32] * 4 + [c_void_p] * 14
+        L.gs_texture_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, POINTER(c_size_t)]
+        L.gs_texture_input_forward.argtypes = [POINTER(GsTextureArgs), c_void_p, c_void_p]
+        L.gs_texture_input_backward.argtypes = [POINTER(GsTextureArgs), c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p,
+                                                c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

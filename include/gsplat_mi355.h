@@ -51,6 +51,7 @@ extern "C" {
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
  *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward,
  *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward,
+ *   gs_texture_input_forward, gs_texture_input_backward,
  *   gs_grad_norm, gs_grad_scale, gs_adam_step_ex (every tensor with a device-resident step number)
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
@@ -617,6 +618,51 @@ int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32
                                const float* dL_dscaling_out, const float* dL_drotation_out, const float* dL_dfeature,
                                const float* dL_dnr_xyz, const float* dL_dnr_scale, const float* dL_dnr_rot,
                                float* dL_ddeltas, float* dL_dscaling, float* dL_drotation, void* stream);
+
+/* ---- the input of the ColorMLP texture (models/texture/texture.py ColorMLP.compose_input): the [N, D] matrix the
+ * colour MLP reads, composed in one launch, and its backward in one launch (plus one small fixed-order sum for the
+ * latent code).  The full semantics, every gradient included, are spelled out at the top of csrc/texture.hip.  All
+ * arrays are fp32, row-major, contiguous.  The columns of `inp`:
+ *   [ before[0] | .. | before[n_before-1] | sh_embed | after[0] | .. | after[n_after-1] | latent ]
+ * before[b] [N, before_w[b]] and after[a] [N, after_w[a]] are copied into place; sh_embed is the (sh_degree + 1)^2 - 1
+ * spherical-harmonics bases above the constant one (utils/sh_utils.py eval_sh_bases(..)[..., 1:]; none at degree 0) of
+ * the unit view direction of models/texture/texture.py:90-101: d = xyz - campos; with fwd_transform, d = R^T d, R the
+ * 3x3 of row n read in place at fwd_transform + n rot_stride, its rows rot_row floats apart ((N, 4, 4): 16 and 4;
+ * (N, 3, 3): 9 and 3); with use_noise, d = d @ noise (row-major, by value); unit = d / (|d| + 1e-12).  latent [latent_dim]
+ * is one row broadcast to every row.  D = the sum of the widths, at most GS_TEXTURE_MAX_D.  The struct is handed to the
+ * kernels by value.
+ * gs_texture_input_forward: a -> inp [N, D].
+ * gs_texture_input_backward: from dL_dinp [N, D] to dL_dbefore[b] / dL_dafter[a] (host arrays of n_before / n_after device
+ *   addresses, the array or any entry NULL = not wanted), dL_dxyz [N, 3] (sh_degree > 0 only) and dL_dlatent [latent_dim]
+ *   (the column sums: per-workgroup partials in `workspace`, gs_texture_workspace_bytes(N, D, latent_dim) bytes, summed in a
+ *   fixed order: bitwise reproducible), any of them NULL = not wanted and then not computed.  fwd_transform, campos and
+ *   noise take no gradient.  Reads of `a`: the widths, and for dL_dxyz what the direction is made of.
+ * N == 0 does nothing.  GS_E_BAD_ARG (before any HIP call): a NULL args, N < 0, sh_degree outside 0..4, n_before over
+ * GS_TEXTURE_MAX_BEFORE, n_after over GS_TEXTURE_MAX_AFTER, a width below 1, latent_dim < 0, D over the cap or not the sum
+ * of the widths, a NULL required pointer or a misaligned one (16 bytes for inp, the blocks and their gradients, else fp32
+ * alignment), rot_row < 3 or rot_stride < 2 rot_row + 3 with a fwd_transform, dL_dxyz at sh_degree 0, dL_dlatent at
+ * latent_dim 0.  GS_E_WORKSPACE: dL_dlatent with a workspace smaller than gs_texture_workspace_bytes says. ---- */
+#define GS_TEXTURE_MAX_D 512
+#define GS_TEXTURE_MAX_BEFORE 6
+#define GS_TEXTURE_MAX_AFTER 2
+typedef struct GsTextureArgs {
+    int32_t N, D;
+    int32_t sh_degree;
+    int32_t n_before, n_after;
+    int32_t before_w[GS_TEXTURE_MAX_BEFORE];
+    int32_t after_w[GS_TEXTURE_MAX_AFTER];
+    int32_t latent_dim;
+    int32_t rot_stride, rot_row;
+    int32_t use_noise;
+    float noise[9];
+    const float* before[GS_TEXTURE_MAX_BEFORE];
+    const float* after[GS_TEXTURE_MAX_AFTER];
+    const float *xyz, *campos, *fwd_transform, *latent;
+} GsTextureArgs;
+int gs_texture_workspace_bytes(int32_t N, int32_t D, int32_t latent_dim, size_t* out);
+int gs_texture_input_forward(const GsTextureArgs* a, float* inp, void* stream);
+int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, float* const* dL_dbefore, float* const* dL_dafter,
+                              float* dL_dxyz, float* dL_dlatent, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
  * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
