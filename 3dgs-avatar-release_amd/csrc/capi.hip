@@ -1165,6 +1165,59 @@ int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, floa
     return launch_texture_input_backward(a, dL_dinp, gr, dL_dxyz, dL_dlatent, workspace, (hipStream_t)stream);
 }
 
+// ---- the fused VanillaCondMLP (mlp.hip)
+static int mlp_validate(const GsMlpArgs* a) {
+    if (!a || a->N < 0 || a->width < 32 || a->width > GS_MLP_MAX_WIDTH || a->width % 32 != 0 || a->n_hidden < 1 ||
+        a->n_hidden > GS_MLP_MAX_HIDDEN || a->dim_in < 1 || a->dim_in > GS_MLP_MAX_IN || a->dim_cond < 0 ||
+        a->dim_cond > GS_MLP_MAX_COND || a->dim_out < 1 || a->dim_out > GS_MLP_MAX_OUT || !(a->slope == a->slope))
+        return GS_E_BAD_ARG;
+    return GS_OK;
+}
+// x, the condition and every layer's parameters
+static bool mlp_inputs_ok(const GsMlpArgs* a) {
+    if (!a->x || !nr_a16(a->x) || (a->dim_cond > 0 && !pose_req(a->cond))) return false;
+    for (int l = 0; l <= a->n_hidden; l++)
+        if (!pose_req(a->W[l]) || !pose_req(a->b[l])) return false;
+    return true;
+}
+int gs_mlp_workspace_bytes(const GsMlpArgs* a, int32_t backward, size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    if (const int rc = mlp_validate(a)) return rc;
+    *out = mlp_workspace_bytes(a, backward != 0);
+    return GS_OK;
+}
+int gs_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mlp_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!mlp_inputs_ok(a) || !pose_req(y) || !nr_a16(acts)) return GS_E_BAD_ARG;
+    if (a->dim_cond > 0) {
+        if (!pose_req(workspace)) return GS_E_BAD_ARG;
+        if (workspace_bytes < mlp_workspace_bytes(a, 0)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_mlp_forward(a, y, acts, workspace, (hipStream_t)stream);
+}
+int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    if (const int rc = mlp_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!mlp_inputs_ok(a) || !acts || !nr_a16(acts) || !dL_dy || !nr_a16(dL_dy) || !pose_a4(a->dx) || !pose_a4(a->dcond))
+        return GS_E_BAD_ARG;
+    if (a->dcond && a->dim_cond == 0) return GS_E_BAD_ARG;
+    bool any = a->dx || a->dcond;
+    for (int l = 0; l <= a->n_hidden; l++) {
+        if (!pose_a4(a->dW[l]) || !pose_a4(a->db[l])) return GS_E_BAD_ARG;
+        any = any || a->dW[l] || a->db[l];
+    }
+    if (any) {
+        if (!workspace || !nr_a16(workspace)) return GS_E_BAD_ARG;
+        if (workspace_bytes < mlp_workspace_bytes(a, 1)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!any) return GS_OK;
+    return launch_mlp_backward(a, acts, dL_dy, workspace, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

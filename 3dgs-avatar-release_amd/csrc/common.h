@@ -715,6 +715,10 @@ size_t texture_workspace_bytes(int N, int D, int latent_dim);
 int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s);
 int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const TxGrads& grads, float* dxyz, float* dlatent,
                                   void* workspace, hipStream_t s);
+// the fused VanillaCondMLP (mlp.hip; the spec is at its top)
+size_t mlp_workspace_bytes(const GsMlpArgs* a, int backward);
+int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, hipStream_t s);
+int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, void* workspace, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

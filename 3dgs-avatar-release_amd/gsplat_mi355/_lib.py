@@ -50,6 +50,7 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
            "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
            "gs_texture_workspace_bytes", "gs_texture_input_forward", "gs_texture_input_backward",
+           "gs_mlp_workspace_bytes", "gs_mlp_forward", "gs_mlp_backward",
            "gs_grad_norm_workspace_bytes", "gs_grad_norm", "gs_grad_scale", "gs_adam_step_ex"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
@@ -137,6 +138,17 @@ class GsTextureArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsTextureArgs
                 ("latent_dim", c_int32), ("rot_stride", c_int32), ("rot_row", c_int32), ("use_noise", c_int32),
                 ("noise", c_float * 9), ("before", c_void_p * GS_TEXTURE_MAX_BEFORE), ("after", c_void_p * GS_TEXTURE_MAX_AFTER),
                 ("xyz", c_void_p), ("campos", c_void_p), ("fwd_transform", c_void_p), ("latent", c_void_p)]
+
+
+# include/gsplat_mi355.h
+GS_MLP_MAX_WIDTH, GS_MLP_MAX_HIDDEN, GS_MLP_MAX_LAYERS, GS_MLP_MAX_IN, GS_MLP_MAX_COND, GS_MLP_MAX_OUT = 128, 6, 7, 512, 512, 64
+GS_MLP_TILE_ROWS, GS_MLP_PARTIAL_MIN_ROWS, GS_MLP_MAX_PARTIALS = 128, 256, 128
+
+
+class GsMlpArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsMlpArgs
+    _fields_ = [(n, c_int32) for n in ("N", "dim_in", "dim_cond", "width", "n_hidden", "dim_out")] + [
+        ("slope", c_float), ("x", c_void_p), ("cond", c_void_p)] + [
+        (n, c_void_p * GS_MLP_MAX_LAYERS) for n in ("W", "b", "dW", "db")] + [("dx", c_void_p), ("dcond", c_void_p)]
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -243,6 +255,9 @@ def load():
         L.gs_texture_input_forward.argtypes = [POINTER(GsTextureArgs), c_void_p, c_void_p]
         L.gs_texture_input_backward.argtypes = [POINTER(GsTextureArgs), c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p,
                                                 c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_mlp_workspace_bytes.argtypes = [POINTER(GsMlpArgs), c_int32, POINTER(c_size_t)]
+        L.gs_mlp_forward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_mlp_backward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

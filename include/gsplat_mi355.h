@@ -51,7 +51,7 @@ extern "C" {
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
  *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward,
  *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward,
- *   gs_texture_input_forward, gs_texture_input_backward,
+ *   gs_texture_input_forward, gs_texture_input_backward, gs_mlp_forward, gs_mlp_backward,
  *   gs_grad_norm, gs_grad_scale, gs_adam_step_ex (every tensor with a device-resident step number)
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
@@ -663,6 +663,53 @@ int gs_texture_workspace_bytes(int32_t N, int32_t D, int32_t latent_dim, size_t*
 int gs_texture_input_forward(const GsTextureArgs* a, float* inp, void* stream);
 int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, float* const* dL_dbefore, float* const* dL_dafter,
                               float* dL_dxyz, float* dL_dlatent, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the dense networks (models/network_utils.py VanillaCondMLP :182-249) as one fused op on the exact-fp32 MFMA:
+ * y = L_{nl-1}(leaky(.. leaky(L_0([x | cond])) ..)), n_hidden hidden layers of one width, nl = n_hidden + 1 nn.Linear
+ * layers, LeakyReLU of `slope` between them and none after the last.  The full semantics, every gradient included, are
+ * spelled out at the top of csrc/mlp.hip.  All arrays are fp32, row-major, contiguous.
+ *
+ * GsMlpArgs (handed to the kernels by value: there is no pointer table in device memory): N rows; dim_in in
+ *   1..GS_MLP_MAX_IN; dim_cond in 0..GS_MLP_MAX_COND; width a multiple of 32 in 32..GS_MLP_MAX_WIDTH; n_hidden in
+ *   1..GS_MLP_MAX_HIDDEN; dim_out in 1..GS_MLP_MAX_OUT; x [N, dim_in] (16-byte aligned); cond [dim_cond], ONE row shared by
+ *   every row of x and never expanded (NULL at dim_cond 0); W[l], b[l] for l = 0..n_hidden: W[0] [width, dim_in + dim_cond],
+ *   W[l] [width, width], W[n_hidden] [dim_out, width].  The gradient addresses dW[l], db[l] (shaped as W[l], b[l]), dx
+ *   [N, dim_in] and dcond [dim_cond] are read by gs_mlp_backward only; NULL = not wanted, and then neither computed nor
+ *   written.
+ * gs_mlp_forward (one launch; one small launch in front of it at dim_cond > 0): y [N, dim_out]; acts [n_hidden, N, width]
+ *   (16-byte aligned), the hidden post-activations gs_mlp_backward reads, NULL = not saved.  `workspace`:
+ *   gs_mlp_workspace_bytes(a, 0) bytes (none at dim_cond 0).
+ * gs_mlp_backward (at most three launches): from dL_dy [N, dim_out] (16-byte aligned) and acts to the wanted gradients.
+ *   `workspace` (16-byte aligned): gs_mlp_workspace_bytes(a, 1) bytes -- the layers' pre-activation gradients and at most
+ *   GS_MLP_MAX_PARTIALS partial parameter gradients, each over max(GS_MLP_PARTIAL_MIN_ROWS, ceil(N / GS_MLP_MAX_PARTIALS)
+ *   rounded up to 32) consecutive rows and summed in index order: no atomics, bitwise reproducible, the partition a
+ *   function of N alone.  A forward tile is GS_MLP_TILE_ROWS rows.
+ * N == 0 does nothing.  GS_E_BAD_ARG (before any HIP call): a NULL args, N < 0, a size outside the ranges above, a NaN
+ *   slope, a NULL required pointer or a misaligned one (16 bytes for x, acts, dL_dy and the backward's workspace, else fp32
+ *   alignment), dcond at dim_cond 0.  GS_E_WORKSPACE: the workspace is smaller than gs_mlp_workspace_bytes says. ---- */
+#define GS_MLP_MAX_WIDTH 128
+#define GS_MLP_MAX_HIDDEN 6
+#define GS_MLP_MAX_LAYERS 7
+#define GS_MLP_MAX_IN 512
+#define GS_MLP_MAX_COND 512
+#define GS_MLP_MAX_OUT 64
+#define GS_MLP_TILE_ROWS 128
+#define GS_MLP_PARTIAL_MIN_ROWS 256
+#define GS_MLP_MAX_PARTIALS 128
+typedef struct GsMlpArgs {
+    int32_t N, dim_in, dim_cond, width, n_hidden, dim_out;
+    float slope;
+    const float *x, *cond;
+    const float* W[GS_MLP_MAX_LAYERS];
+    const float* b[GS_MLP_MAX_LAYERS];
+    float* dW[GS_MLP_MAX_LAYERS];
+    float* db[GS_MLP_MAX_LAYERS];
+    float *dx, *dcond;
+} GsMlpArgs;
+int gs_mlp_workspace_bytes(const GsMlpArgs* a, int32_t backward, size_t* out);
+int gs_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, size_t workspace_bytes, void* stream);
+int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
  * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
