@@ -18,6 +18,42 @@ def cloud_and_camera(n, W, H, sh_degree=3, seed=0, frame=0, dist2_fn=None, heavy
     return cloud, cam
 
 
+POSES = {  # name -> (yaw, pitch, roll), T, (kx, ky): what cloud_and_camera's orbit camera never has
+    # every entry of the 3x3 block non-zero, fx != fy, off-axis translation
+    "general": ((0.7, -0.4, 0.9), (0.3, -0.2, 3.2), (1.0, 1.31)),
+    # camera inside the [-1, 1]^3 cloud: near-plane culls, huge on-screen radii with clamped rects, both Jacobian clamps
+    "inside": ((-2.1, 0.6, -1.3), (0.1, 0.15, 0.4), (0.8, 1.0)),
+    # x and y axes exchanged, fx != fy
+    "roll90": ((0.0, 0.0, math.pi / 2), (0.0, 0.0, 3.0), (1.2, 0.9)),
+}
+
+
+def posed_camera(name, W, H):
+    """A named general camera: R = Ry(yaw) Rx(pitch) Rz(roll) (camera-to-world, as Camera takes it), translation T, and
+    focal lengths kx f, ky f with f = 500 W / 512 (the orbit camera's), so that FoVx and FoVy come from different focal
+    lengths as the reference's real cameras' do."""
+    (yaw, pitch, roll), T, (kx, ky) = POSES[name]
+    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
+    Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cp, -sp], [0.0, sp, cp]])
+    Rz = np.array([[cr, -sr, 0.0], [sr, cr, 0.0], [0.0, 0.0, 1.0]])
+    f = 500.0 * W / 512.0
+    return Camera(Ry @ Rx @ Rz, np.array(T), focal2fov(kx * f, W), focal2fov(ky * f, H), W, H)
+
+
+def view_stats(cloud, cam):
+    """What a camera makes of a cloud, in float64 from xyz @ world_view_transform: `culled` = points at or behind the
+    0.2 near plane, `xclamp` / `yclamp` = visible points beyond the 1.3 tanfov clamp of the projection Jacobian in x / y.
+    The tests under general cameras assert these before they compare anything."""
+    wv = cam.world_view_transform.cpu().numpy().astype(np.float64)
+    p = cloud.xyz.cpu().numpy().astype(np.float64) @ wv[:3, :3] + wv[3, :3]
+    vis = p[:, 2] > 0.2
+    z = np.where(vis, p[:, 2], 1.0)
+    return dict(culled=int((~vis).sum()),
+                xclamp=int((vis & (np.abs(p[:, 0] / z) > 1.3 * math.tan(cam.FoVx * 0.5))).sum()),
+                yclamp=int((vis & (np.abs(p[:, 1] / z) > 1.3 * math.tan(cam.FoVy * 0.5))).sum()))
+
+
 def needle_cloud_and_camera(n, W, H, seed=0, major=(0.15, 0.7), sh_degree=1):
     """Long thin Gaussians lying in the image plane (sigma_major hundreds of pixels, sigma_minor at the 0.3 px^2
     low-pass floor, random in-plane angles): their 2-D covariance determinant is a difference of nearly equal numbers,

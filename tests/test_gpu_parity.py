@@ -15,7 +15,10 @@ oracle's own walk reproduce the device's pixel -- unattributed pixels = 0 is ass
 ALL gradients are then compared with the oracle CONDITIONED on those decisions (the same arithmetic, the named
 near-threshold decisions taken the device's way), with no exempt fraction for the image and n_contrib.  The smaller
 tests keep the older form: a bulk bound (<= 1e-5 of the tensor maximum for all but a small fraction of the elements)
-plus a cap on the outliers (<= 1e-2 absolute for the image)."""
+plus a cap on the outliers (<= 1e-2 absolute for the image).
+
+Every scene here is seen through the orbit camera with scale_modifier 1: pose coverage (fx != fy, pitch and roll, the
+camera inside the cloud) and modifier coverage live in test_gpu_cameras.py."""
 import math
 import os
 
