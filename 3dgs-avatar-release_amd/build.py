@@ -23,19 +23,20 @@ COMMON = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-fhip-fp32-co
           "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # translation units whose integer outputs must match the CPU oracle bit for bit (aiap: whose sign decisions must see
 # equal distances as equal; hashgrid: whose cells and table entries must match the float64 restatement; skinning: whose
-# one-hot weights must give T_fwd rows equal to the bone transforms; pose: whose joints off the leg chains must carry the
+# one-hot weights must give T_fwd rows equal to the bone transforms; skinloss: whose face picks must match the float64
+# restatement's and whose sums are written in one order; pose: whose joints off the leg chains must carry the
 # chain's rotation unchanged and whose sums are written in one order; nonrigid: whose sums are written in one order and
 # whose ReLU and clamp decisions must see what the float64 restatement sees; texture: whose latent sums are written in one
 # order and whose bases are the polynomials as written; mlp: whose condition, bias and final sums are written in one order --
 # its matrix products are MFMA instructions either way): no FMA contraction
-STRICT = {"preprocess.hip", "knn.hip", "densify.hip", "aiap.hip", "hashgrid.hip", "skinning.hip", "pose.hip", "nonrigid.hip",
-          "texture.hip", "mlp.hip"}
+STRICT = {"preprocess.hip", "knn.hip", "densify.hip", "aiap.hip", "hashgrid.hip", "skinning.hip", "skinloss.hip", "pose.hip",
+          "nonrigid.hip", "texture.hip", "mlp.hip"}
 # packed fp32 (v_pk_*) issues at half rate on gfx950 (tools/valu_rate.hip), so pairing scalars buys
 # nothing and the register shuffling the SLP vectoriser adds to form the pairs costs VALU slots
 NO_SLP = {"render_fwd.hip", "render_bwd.hip"}
 SOURCES = ["capi.hip", "preprocess.hip", "radix_sort.hip", "depth_sort.hip", "binning.hip", "render_fwd.hip", "render_bwd.hip",
            "gaussian_bwd.hip", "knn.hip", "loss.hip", "prepass.hip", "optim.hip", "densify.hip", "aiap.hip", "hashgrid.hip",
-           "skinning.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "debug_stats.hip"]
+           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "debug_stats.hip"]
 
 
 def hipcc():

@@ -974,6 +974,49 @@ int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* t
                                     dL_drotation, workspace, (hipStream_t)stream);
 }
 
+// ---- the skinning regulariser (skinloss.hip)
+static bool skin_loss_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX; }
+int gs_mesh_sample(int32_t n, int32_t V, int32_t F, const float* verts, const int32_t* faces, const float* cdf,
+                   const float* vweights, const float* aabb_min, const float* aabb_inv_extent, const float* draws,
+                   float* points_norm, float* target, int32_t* face, float* bary, float* points, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || V < 1 || F < 1) return GS_E_BAD_ARG;
+    if (!verts || !faces || !cdf || !vweights || !aabb_min || !aabb_inv_extent) return GS_E_BAD_ARG;
+    if (!skin_a4(verts) || !skin_a4(faces) || !skin_a4(cdf) || !skin_a16(vweights) || !skin_a4(aabb_min) ||
+        !skin_a4(aabb_inv_extent))
+        return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!draws || !points_norm || !target) return GS_E_BAD_ARG;
+    if (!skin_a4(draws) || !skin_a16(points_norm) || !skin_a16(target) || !skin_a4(face) || !skin_a16(bary) || !skin_a16(points))
+        return GS_E_BAD_ARG;
+    return launch_mesh_sample(n, V, F, verts, faces, cdf, vweights, aabb_min, aabb_inv_extent, draws, points_norm, target, face,
+                              bary, points, (hipStream_t)stream);
+}
+int gs_skin_loss_workspace_bytes(int32_t n, size_t* out) {
+    if (!out || n < 0) return GS_E_BAD_ARG;
+    *out = skin_loss_workspace_bytes(n);
+    return GS_OK;
+}
+int gs_skin_loss_forward(int32_t n, int32_t kind, const float* logits, const float* target, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!logits || !target || !loss || !workspace) return GS_E_BAD_ARG;
+    if (!skin_a16(logits) || !skin_a16(target) || !skin_a4(loss) || !skin_a16(workspace)) return GS_E_BAD_ARG;
+    if (workspace_bytes < skin_loss_workspace_bytes(n)) return GS_E_WORKSPACE;
+    return launch_skin_loss_forward(n, kind, logits, target, loss, workspace, (hipStream_t)stream);
+}
+int gs_skin_loss_backward(int32_t n, int32_t kind, const float* logits, const float* target, const float* dL_dloss,
+                          float* dL_dlogits, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!logits || !target || !dL_dloss || !dL_dlogits) return GS_E_BAD_ARG;
+    if (!skin_a16(logits) || !skin_a16(target) || !skin_a4(dL_dloss) || !skin_a16(dL_dlogits)) return GS_E_BAD_ARG;
+    return launch_skin_loss_backward(n, kind, logits, target, dL_dloss, dL_dlogits, (hipStream_t)stream);
+}
+
 // ---- SMPL pose correction (pose.hip)
 static bool pose_a4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 static bool pose_req(const void* p) { return p && pose_a4(p); }

@@ -686,6 +686,15 @@ int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, c
 int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
                              const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
                              void* workspace, hipStream_t s);
+// the skinning regulariser: mesh surface samples and the fused loss (skinloss.hip; the spec is at its top)
+size_t skin_loss_workspace_bytes(int n);
+int launch_mesh_sample(int n, int V, int F, const float* verts, const int* faces, const float* cdf, const float* vweights,
+                       const float* aabb_min, const float* aabb_inv_extent, const float* draws, float* p_norm, float* target,
+                       int* face, float* bary, float* points, hipStream_t s);
+int launch_skin_loss_forward(int n, int kind, const float* logits, const float* target, float* loss, void* workspace,
+                             hipStream_t s);
+int launch_skin_loss_backward(int n, int kind, const float* logits, const float* target, const float* dL_dloss,
+                              float* dL_dlogits, hipStream_t s);
 // SMPL pose correction (pose.hip; the spec is at its top)
 size_t pose_workspace_bytes(int V);
 int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone, float* loss, float* state, void* workspace,

@@ -46,6 +46,7 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward",
            "gs_skin_weights_forward", "gs_skin_weights_backward", "gs_skinning_workspace_bytes", "gs_skinning_forward",
            "gs_skinning_backward",
+           "gs_mesh_sample", "gs_skin_loss_workspace_bytes", "gs_skin_loss_forward", "gs_skin_loss_backward",
            "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward",
            "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
            "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
@@ -241,6 +242,10 @@ def load():
                                           c_void_p]
         L.gs_skinning_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_mesh_sample.argtypes = [c_int32, c_int32, c_int32] + [c_void_p] * 13
+        L.gs_skin_loss_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
+        L.gs_skin_loss_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_skin_loss_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_pose_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
         L.gs_pose_forward.argtypes = [POINTER(GsPoseArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]

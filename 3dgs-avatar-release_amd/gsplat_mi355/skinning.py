@@ -10,8 +10,17 @@ reproducible), no host synchronisation, capture-safe.
 * `linear_blend_skinning(w, tfs, xyz, rotation, weights=False)` -> (xyz_bar, rotation_bar, T_fwd).
 * `skinning_field_forward(field, gaussians, iteration, camera)` -- SkinningField.forward with the fused op
   (INTEGRATION.md: `SkinningField.forward = skinning_field_forward`).
+
+The skinning regulariser (csrc/skinloss.hip, whose header comment carries its spec) on the device as well:
+* `MeshSampler(verts, faces, vertex_weights, aabb_min, aabb_max, device)` -- area-weighted surface samples of a mesh with
+  their blended skinning weights, one launch per `sample(n)`.
+* `skinning_mse_loss(logits, target)` -- mse_loss(softmax(logits), target, 'none').sum(-1).mean() as one autograd node:
+  two launches forward, one backward, summed in a fixed order (bitwise reproducible), capture-safe.
+* `skinning_loss(field, draws=None)` -- SkinningField.get_skinning_loss
+  (INTEGRATION.md: `SkinningField.get_skinning_loss = skinning_loss`).
 Device fp32 tensors only: there is no CPU path.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -165,3 +174,148 @@ def skinning_field_forward(field, gaussians, iteration, camera):
     deformed_gaussians._xyz = xyz_bar
     setattr(deformed_gaussians, "rotation_precomp", rotation_bar)
     return deformed_gaussians
+
+
+class _SkinLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, kind):
+        x = _lib.contiguous_aligned(_dev32(logits, "logits"))
+        tg = _lib.contiguous_aligned(_dev32(target, "target"))
+        dev, n = x.device, int(x.shape[0])
+        ctx.save_for_backward(x, tg)
+        ctx.kind = kind
+        if n == 0:  # nothing to launch: 0, not torch's nan for an empty mean
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        L = _lib.load()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.nbytes(L.gs_skin_loss_workspace_bytes, n), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(L.gs_skin_loss_forward(n, kind, _lib.ptr(x), _lib.ptr(tg), loss.data_ptr(), _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_ptr(dev)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, tg = ctx.saved_tensors
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        dev, n = x.device, int(x.shape[0])
+        dx = torch.empty_like(x)
+        if n == 0:
+            return dx, None, None
+        g = g.to(torch.float32).contiguous()  # stays on the device: the kernel reads it there
+        with _lib.on_device(dev):
+            _lib.check(_lib.load().gs_skin_loss_backward(n, ctx.kind, _lib.ptr(x), _lib.ptr(tg), g.data_ptr(), _lib.ptr(dx),
+                                                         _lib.stream_ptr(dev)))
+        return dx, None, None
+
+
+def skinning_mse_loss(logits, target):
+    """get_skinning_loss's tail as one autograd node: W = hierarchical_softmax(logits) for (n, 25) logits, F.softmax for
+    (n, 24), anything else ValueError; the result is mse_loss(W, target, reduction='none').sum(-1).mean() as a 0-d
+    tensor.  The rows are summed in a fixed order in double (bitwise reproducible); `target` (n, 24) gets no gradient.
+    n = 0 gives 0 (torch's mean over no rows would give nan)."""
+    if logits.dim() != 2 or logits.shape[1] not in (24, 25):
+        raise ValueError("skinning_mse_loss: (n, 25) or (n, 24) logits expected, got %s" % (tuple(logits.shape),))
+    if tuple(target.shape) != (int(logits.shape[0]), BONES):
+        raise ValueError("skinning_mse_loss: target must be (%d, 24), got %s" % (int(logits.shape[0]), tuple(target.shape)))
+    _dev32(logits, "logits")
+    _dev32(target, "target")
+    if target.device != logits.device:
+        raise RuntimeError("skinning_mse_loss: logits and target live on different devices")
+    kind = _lib.GS_SKIN_HIERARCHICAL if logits.shape[1] == 25 else _lib.GS_SKIN_SOFTMAX
+    return _SkinLoss.apply(logits, target, kind)
+
+
+def _np(a, dtype):
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a), dtype=dtype)
+
+
+class MeshSampler(object):
+    """Area-weighted surface samples of a triangle mesh with their barycentrically blended per-vertex skinning weights
+    (SkinningField.sample_skinning_loss: trimesh's sample_surface, igl's barycentric coordinates and the numpy blend), on
+    the device.  Built once from numpy arrays or tensors: `verts` (V, 3), `faces` (F, 3), `vertex_weights` (V, 24), and the
+    box `aabb_min`, `aabb_max` (3) of AABB.normalize.  The face areas and their cumulative sum are computed in float64 from
+    the fp32 vertices and rounded to fp32 once.  Public buffers (device tensors): `verts`, `faces` (int32), `cdf`,
+    `vertex_weights`, `aabb_min`, `aabb_inv_extent`."""
+
+    def __init__(self, verts, faces, vertex_weights, aabb_min, aabb_max, device):
+        v = _np(verts, np.float32)
+        f = _np(faces, np.int64)
+        w = _np(vertex_weights, np.float32)
+        lo, hi = _np(aabb_min, np.float32).reshape(-1), _np(aabb_max, np.float32).reshape(-1)
+        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1:
+            raise ValueError("MeshSampler: verts must be (V, 3) with V >= 1, got %s" % (v.shape,))
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+            raise ValueError("MeshSampler: faces must be (F, 3) with F >= 1, got %s" % (f.shape,))
+        if w.shape != (v.shape[0], BONES):
+            raise ValueError("MeshSampler: vertex_weights must be (%d, 24), got %s" % (v.shape[0], w.shape))
+        if f.min() < 0 or f.max() >= v.shape[0]:
+            raise ValueError("MeshSampler: faces index vertices outside [0, %d)" % v.shape[0])
+        if lo.shape != (3,) or hi.shape != (3,) or not (hi > lo).all():
+            raise ValueError("MeshSampler: aabb_min < aabb_max, three values each, expected")
+        v64 = v.astype(np.float64)
+        e1, e2 = v64[f[:, 1]] - v64[f[:, 0]], v64[f[:, 2]] - v64[f[:, 0]]
+        area = 0.5 * np.sqrt((np.cross(e1, e2) ** 2).sum(1))
+        if not np.isfinite(area).all() or not area.sum() > 0:
+            raise ValueError("MeshSampler: the mesh has no finite positive area")
+        cdf = np.cumsum(area).astype(np.float32)
+        inv = (1.0 / (hi.astype(np.float64) - lo.astype(np.float64))).astype(np.float32)
+        self.device = torch.device(device)
+        to = lambda a: torch.from_numpy(a).to(self.device)
+        self.verts, self.faces, self.cdf = to(v), to(f.astype(np.int32)), to(cdf)
+        self.vertex_weights, self.aabb_min, self.aabb_inv_extent = to(w), to(lo), to(inv)
+
+    def sample(self, n, draws=None, generator=None, return_index=False):
+        """(points_norm (n, 3), target (n, 24)): the samples in the box's [-1, 1] coordinates and their skinning weights;
+        with return_index also (face (n) int32, bary (n, 3), points (n, 3)).  `draws` (n, 3), uniform in [0, 1): the face
+        pick and the two barycentric draws of every sample; None draws them with torch.rand on the device (`generator`),
+        one launch.  The distribution is trimesh's; the random stream is torch's, not numpy's: a run does not reproduce
+        the reference's samples draw for draw.  An explicit `draws` pins everything."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("MeshSampler.sample: n >= 0 expected")
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("MeshSampler.sample: the mesh must live on the GPU (the fused HIP kernels have no CPU fallback)")
+        if draws is None:
+            draws = torch.rand((n, 3), dtype=torch.float32, device=dev, generator=generator)
+        else:
+            if tuple(draws.shape) != (n, 3):
+                raise ValueError("MeshSampler.sample: draws must be (%d, 3), got %s" % (n, tuple(draws.shape)))
+            draws = _dev32(draws, "draws").contiguous()
+            if draws.device != dev:
+                raise RuntimeError("MeshSampler.sample: draws live on another device than the mesh")
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        points_norm, target = new(n, 3), new(n, BONES)
+        face, bary, points = (new(n, dtype=torch.int32), new(n, 3), new(n, 3)) if return_index else (None, None, None)
+        with _lib.on_device(dev):
+            _lib.check(_lib.load().gs_mesh_sample(
+                n, int(self.verts.shape[0]), int(self.faces.shape[0]), _lib.ptr(self.verts), _lib.ptr(self.faces),
+                _lib.ptr(self.cdf), _lib.ptr(self.vertex_weights), _lib.ptr(self.aabb_min), _lib.ptr(self.aabb_inv_extent),
+                _lib.ptr(draws), _lib.ptr(points_norm), _lib.ptr(target), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(points),
+                _lib.stream_ptr(dev)))
+        if return_index:
+            return points_norm, target, face, bary, points
+        return points_norm, target
+
+
+def skinning_loss(field, draws=None):
+    """SkinningField.get_skinning_loss (models/deformer/rigid.py:198-212) on the device: `field.cfg.n_reg_pts` surface
+    samples (or one per row of `draws`, see MeshSampler.sample), field.lbs_network on their normalised positions, and
+    `skinning_mse_loss` against their sampled weights.  The sampler is built at the first call from field.smpl_verts,
+    field.faces, field.skinning_weights and field.aabb (coord_min, coord_max) and kept on the module as
+    `_gsplat_mesh_sampler`.  The voxel-grid path (field.distill) is not supported."""
+    if getattr(field, "distill", False):
+        raise NotImplementedError("skinning_loss: the distill (voxel-grid) path is not supported")
+    sampler = field.__dict__.get("_gsplat_mesh_sampler")
+    if sampler is None:
+        aabb = field.aabb
+        sampler = MeshSampler(field.smpl_verts, field.faces, field.skinning_weights, aabb.coord_min, aabb.coord_max,
+                              aabb.coord_min.device)
+        field.__dict__["_gsplat_mesh_sampler"] = sampler
+    n = int(draws.shape[0]) if draws is not None else int(field.cfg.n_reg_pts)
+    points_norm, target = sampler.sample(n, draws=draws)
+    return skinning_mse_loss(field.lbs_network(points_norm), target)

@@ -49,7 +49,8 @@ extern "C" {
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
- *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_pose_forward, gs_pose_backward,
+ *   gs_skin_weights_backward, gs_skinning_forward, gs_skinning_backward, gs_mesh_sample, gs_skin_loss_forward,
+ *   gs_skin_loss_backward, gs_pose_forward, gs_pose_backward,
  *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward,
  *   gs_texture_input_forward, gs_texture_input_backward, gs_mlp_forward, gs_mlp_backward,
  *   gs_grad_norm, gs_grad_scale, gs_adam_step_ex (every tensor with a device-resident step number)
@@ -519,6 +520,35 @@ int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tf
 int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
                          const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
                          float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the rigid deformer's skinning regulariser (models/deformer/rigid.py: SkinningField.sample_skinning_loss and
+ * get_skinning_loss; AABB.normalize at utils/dataset_utils.py:72-76): surface samples of the canonical mesh with their
+ * blended skinning weights, and the mean over rows of the summed squared error between the activated logits and those
+ * weights.  The full semantics (face pick, the fold of the barycentric draws, the summation orders, the gradient) are
+ * spelled out at the top of csrc/skinloss.hip.  All arrays are contiguous, row-major device arrays.
+ * gs_mesh_sample: n samples from draws [n, 3] (fp32 uniforms in [0, 1): the caller's random stream) on the mesh verts
+ *   [V, 3] fp32, faces [F, 3] int32, with cdf [F] fp32 the non-decreasing cumulative face areas (cdf[F-1] the total) and
+ *   vweights [V, 24] fp32 the vertices' skinning weights; aabb_min [3] and aabb_inv_extent [3] fp32.  Writes points_norm
+ *   [n, 3] (the samples in the box's [-1, 1] coordinates) and target [n, 24]; face [n] int32, bary [n, 3] and points
+ *   [n, 3] (unnormalised) are optional (NULL = not wanted).  Vertex indices outside [0, V) are clamped into it.
+ * gs_skin_loss_forward: loss [1] = sum_i sum_j (W_ij - target_ij)^2 / n with W the activation of logits ([n, 25]
+ *   GS_SKIN_HIERARCHICAL or [n, 24] GS_SKIN_SOFTMAX) and target [n, 24]; summed in a fixed order in double through
+ *   `workspace` (gs_skin_loss_workspace_bytes(n): one double per block of 256 rows).
+ * gs_skin_loss_backward: dL_dlogits (shaped as logits) from dL_dloss [1], a DEVICE scalar; recomputes W, keeps nothing
+ *   from the forward, writes every row once.  The target gets no gradient.
+ * n = 0 enqueues nothing and leaves `loss` as it is (the Python layer returns 0, not torch's nan for an empty mean).
+ * Alignment: logits, dL_dlogits, target, vweights, points_norm, bary, points and the workspace need 16 bytes; the other
+ * arrays their element's.  GS_E_BAD_ARG (before any HIP call): n < 0, V < 1, F < 1, an unknown kind (GS_SKIN_WEIGHTS
+ * included), a NULL required pointer or a misaligned one.  GS_E_WORKSPACE: the workspace is smaller than
+ * gs_skin_loss_workspace_bytes(n). ---- */
+int gs_mesh_sample(int32_t n, int32_t V, int32_t F, const float* verts, const int32_t* faces, const float* cdf,
+                   const float* vweights, const float* aabb_min, const float* aabb_inv_extent, const float* draws,
+                   float* points_norm, float* target, int32_t* face, float* bary, float* points, void* stream);
+int gs_skin_loss_workspace_bytes(int32_t n, size_t* out);
+int gs_skin_loss_forward(int32_t n, int32_t kind, const float* logits, const float* target, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gs_skin_loss_backward(int32_t n, int32_t kind, const float* logits, const float* target, const float* dL_dloss,
+                          float* dL_dlogits, void* stream);
 
 /* ---- SMPL pose correction of `pose_correction: direct` (models/pose_correction/pose_correction.py:
  * DirectPoseOptimization.pose_correct through PoseCorrection._forward_smpl, get_transforms_02v and
