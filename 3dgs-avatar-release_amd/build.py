@@ -28,15 +28,16 @@ COMMON = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-fhip-fp32-co
 # chain's rotation unchanged and whose sums are written in one order; nonrigid: whose sums are written in one order and
 # whose ReLU and clamp decisions must see what the float64 restatement sees; texture: whose latent sums are written in one
 # order and whose bases are the polynomials as written; mlp: whose condition, bias and final sums are written in one order --
-# its matrix products are MFMA instructions either way): no FMA contraction
+# its matrix products are MFMA instructions either way; lpips: whose bias, mean and head sums are written in one order -- its
+# products are MFMA instructions either way): no FMA contraction
 STRICT = {"preprocess.hip", "knn.hip", "densify.hip", "aiap.hip", "hashgrid.hip", "skinning.hip", "skinloss.hip", "pose.hip",
-          "nonrigid.hip", "texture.hip", "mlp.hip"}
+          "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip"}
 # packed fp32 (v_pk_*) issues at half rate on gfx950 (tools/valu_rate.hip), so pairing scalars buys
 # nothing and the register shuffling the SLP vectoriser adds to form the pairs costs VALU slots
 NO_SLP = {"render_fwd.hip", "render_bwd.hip"}
 SOURCES = ["capi.hip", "preprocess.hip", "radix_sort.hip", "depth_sort.hip", "binning.hip", "render_fwd.hip", "render_bwd.hip",
            "gaussian_bwd.hip", "knn.hip", "loss.hip", "prepass.hip", "optim.hip", "densify.hip", "aiap.hip", "hashgrid.hip",
-           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "debug_stats.hip"]
+           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip", "debug_stats.hip"]
 
 
 def hipcc():

@@ -1261,6 +1261,82 @@ int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, v
     return launch_mlp_backward(a, acts, dL_dy, workspace, (hipStream_t)stream);
 }
 
+// ---- the LPIPS-VGG perceptual loss (lpips.hip)
+static bool lp_a16(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
+static int lpips_validate(const GsLpipsArgs* a) {
+    if (!a || a->H < GS_LPIPS_MIN_SIZE || a->H > GS_LPIPS_MAX_SIZE || a->W < GS_LPIPS_MIN_SIZE || a->W > GS_LPIPS_MAX_SIZE)
+        return GS_E_BAD_ARG;
+    if (!pose_req(a->in0) || !pose_req(a->in1) || !lp_a16(a->packed)) return GS_E_BAD_ARG;
+    if (a->cs0 < 1 || a->cs1 < 1 || a->rs0 < a->W || a->rs1 < a->W) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_lpips_packed_bytes(size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    *out = lpips_packed_bytes();
+    return GS_OK;
+}
+int gs_lpips_pack_weights(const GsLpipsArgs* a, void* packed, size_t packed_bytes, void* stream) {
+    if (!a || !lp_a16(packed) || !pose_a4(a->shift) || !pose_a4(a->scale)) return GS_E_BAD_ARG;
+    for (int l = 0; l < GS_LPIPS_LAYERS; l++)
+        if (!pose_req(a->weight[l]) || !pose_req(a->bias[l])) return GS_E_BAD_ARG;
+    for (int k = 0; k < GS_LPIPS_TAPS; k++)
+        if (!pose_req(a->lin[k])) return GS_E_BAD_ARG;
+    if (packed_bytes < lpips_packed_bytes()) return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_pack(a, (float*)packed, (hipStream_t)stream);
+}
+int gs_lpips_workspace_bytes(int32_t H, int32_t W, int32_t need_grad0, int32_t need_grad1, int32_t which, size_t* out) {
+    if (!out || H < GS_LPIPS_MIN_SIZE || H > GS_LPIPS_MAX_SIZE || W < GS_LPIPS_MIN_SIZE || W > GS_LPIPS_MAX_SIZE || which < 0 ||
+        which > GS_LPIPS_WS_BACKWARD)
+        return GS_E_BAD_ARG;
+    *out = lpips_workspace_bytes(H, W, need_grad0, need_grad1, which);
+    return GS_OK;
+}
+int gs_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, void* saved, size_t saved_bytes, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (const int rc = lpips_validate(a)) return rc;
+    if (!pose_req(loss) || !pose_a4(per_tap) || !lp_a16(workspace)) return GS_E_BAD_ARG;
+    const size_t need_saved = lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED);
+    if (need_saved && !lp_a16(saved)) return GS_E_BAD_ARG;
+    if (saved_bytes < need_saved ||
+        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_FORWARD))
+        return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_forward(a, loss, per_tap, (float*)saved, (float*)workspace, (hipStream_t)stream);
+}
+int gs_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const void* saved,
+                      size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = lpips_validate(a)) return rc;
+    if (!pose_a4(dL_dloss) || !pose_a4(d_in0) || !pose_a4(d_in1)) return GS_E_BAD_ARG;
+    if ((d_in0 && !a->need_grad0) || (d_in1 && !a->need_grad1)) return GS_E_BAD_ARG;
+    if (!d_in0 && !d_in1) return GS_OK;
+    if (!lp_a16(saved) || !lp_a16(workspace)) return GS_E_BAD_ARG;
+    if (saved_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED) ||
+        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_BACKWARD))
+        return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_backward(a, dL_dloss, d_in0, d_in1, (const float*)saved, (float*)workspace, (hipStream_t)stream);
+}
+int gs_lpips_conv(const float* packed, int32_t layer, int32_t backward, int32_t normalize, int32_t H, int32_t W, const float* in,
+                  int64_t in_cs, int64_t in_rs, const float* mask, float* out, void* stream) {
+    if (!lp_a16(packed) || layer < 0 || layer >= GS_LPIPS_LAYERS || H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE || W > GS_LPIPS_MAX_SIZE)
+        return GS_E_BAD_ARG;
+    const bool image_in = layer == 0 && !backward, image_out = layer == 0 && backward;
+    if (image_in ? (!pose_req(in) || in_cs < 1 || in_rs < W) : !lp_a16(in)) return GS_E_BAD_ARG;
+    if (image_out ? !pose_req(out) : !lp_a16(out)) return GS_E_BAD_ARG;
+    if (backward && !lp_a16(mask)) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_conv(packed, layer, backward, normalize, H, W, in, in_cs, in_rs, mask, out, (hipStream_t)stream);
+}
+int gs_lpips_pool(int32_t backward, int32_t H, int32_t W, int32_t C, const float* in, const float* g, const float* dp, float* out,
+                  void* stream) {
+    if (H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE || W > GS_LPIPS_MAX_SIZE || C < 4 || C > 512 || (C & 3) || !lp_a16(in) || !lp_a16(out))
+        return GS_E_BAD_ARG;
+    if (backward && (!lp_a16(g) || ((H >> 1) && (W >> 1) && !lp_a16(dp)))) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_pool(backward, H, W, C, in, g, dp, out, (hipStream_t)stream);
+}
+
 int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
                void* workspace, size_t workspace_bytes, void* stream) {
     GS_NO_CAPTURE(stream);

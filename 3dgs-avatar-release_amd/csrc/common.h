@@ -728,6 +728,17 @@ int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const 
 size_t mlp_workspace_bytes(const GsMlpArgs* a, int backward);
 int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, hipStream_t s);
 int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, void* workspace, hipStream_t s);
+// the LPIPS-VGG perceptual loss (lpips.hip; the spec is at its top)
+size_t lpips_packed_bytes();
+size_t lpips_workspace_bytes(int H, int W, int grad0, int grad1, int which);
+int lpips_conv_workgroups(int H, int W, int N, int nimg);
+int launch_lpips_pack(const GsLpipsArgs* a, float* packed, hipStream_t s);
+int launch_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, float* saved, float* ws, hipStream_t s);
+int launch_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const float* saved, float* ws,
+                          hipStream_t s);
+int launch_lpips_conv(const float* packed, int layer, int backward, int normalize, int H, int W, const float* in, long long in_cs,
+                      long long in_rs, const float* mask, float* out, hipStream_t s);
+int launch_lpips_pool(int backward, int H, int W, int C, const float* in, const float* g, const float* dp, float* out, hipStream_t s);
 // K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
 int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                       void* ws, size_t ws_bytes, hipStream_t s);

@@ -52,6 +52,8 @@ EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_s
            "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
            "gs_texture_workspace_bytes", "gs_texture_input_forward", "gs_texture_input_backward",
            "gs_mlp_workspace_bytes", "gs_mlp_forward", "gs_mlp_backward",
+           "gs_lpips_packed_bytes", "gs_lpips_pack_weights", "gs_lpips_workspace_bytes", "gs_lpips_forward", "gs_lpips_backward",
+           "gs_lpips_conv", "gs_lpips_pool",
            "gs_grad_norm_workspace_bytes", "gs_grad_norm", "gs_grad_scale", "gs_adam_step_ex"]
 
 GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
@@ -150,6 +152,17 @@ class GsMlpArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsMlpArgs
     _fields_ = [(n, c_int32) for n in ("N", "dim_in", "dim_cond", "width", "n_hidden", "dim_out")] + [
         ("slope", c_float), ("x", c_void_p), ("cond", c_void_p)] + [
         (n, c_void_p * GS_MLP_MAX_LAYERS) for n in ("W", "b", "dW", "db")] + [("dx", c_void_p), ("dcond", c_void_p)]
+
+
+GS_LPIPS_LAYERS, GS_LPIPS_TAPS, GS_LPIPS_MIN_SIZE, GS_LPIPS_MAX_SIZE = 13, 5, 16, 2048  # include/gsplat_mi355.h
+GS_LPIPS_WS_FORWARD, GS_LPIPS_WS_SAVED, GS_LPIPS_WS_BACKWARD = 0, 1, 2
+
+
+class GsLpipsArgs(ctypes.Structure):  # include/gsplat_mi355.h: GsLpipsArgs
+    _fields_ = [(n, c_int32) for n in ("H", "W", "normalize", "need_grad0", "need_grad1")] + [
+        (n, c_int64) for n in ("cs0", "rs0", "cs1", "rs1")] + [(n, c_void_p) for n in ("in0", "in1", "packed")] + [
+        ("weight", c_void_p * GS_LPIPS_LAYERS), ("bias", c_void_p * GS_LPIPS_LAYERS), ("lin", c_void_p * GS_LPIPS_TAPS),
+        ("shift", c_void_p), ("scale", c_void_p)]
 
 
 class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
@@ -263,6 +276,15 @@ def load():
         L.gs_mlp_workspace_bytes.argtypes = [POINTER(GsMlpArgs), c_int32, POINTER(c_size_t)]
         L.gs_mlp_forward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.gs_mlp_backward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.gs_lpips_packed_bytes.argtypes = [POINTER(c_size_t)]
+        L.gs_lpips_pack_weights.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_size_t, c_void_p]
+        L.gs_lpips_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
+        L.gs_lpips_forward.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
+        L.gs_lpips_backward.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                        c_void_p]
+        L.gs_lpips_conv.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p,
+                                    c_void_p, c_void_p]
+        L.gs_lpips_pool.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
         L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]

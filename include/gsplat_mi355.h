@@ -53,6 +53,7 @@ extern "C" {
  *   gs_skin_loss_backward, gs_pose_forward, gs_pose_backward,
  *   gs_pose_encoder_forward, gs_pose_encoder_backward, gs_nonrigid_apply_forward, gs_nonrigid_apply_backward,
  *   gs_texture_input_forward, gs_texture_input_backward, gs_mlp_forward, gs_mlp_backward,
+ *   gs_lpips_forward, gs_lpips_backward, gs_lpips_conv, gs_lpips_pool,
  *   gs_grad_norm, gs_grad_scale, gs_adam_step_ex (every tensor with a device-resident step number)
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
@@ -740,6 +741,64 @@ int gs_mlp_workspace_bytes(const GsMlpArgs* a, int32_t backward, size_t* out);
 int gs_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, size_t workspace_bytes, void* stream);
 int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* ---- the LPIPS-VGG perceptual loss (train.py:28,62-64,127-138 `lpips.LPIPS(net='vgg')`; utils/general_utils.py:279-291):
+ * the input transform, the thirteen 3x3 convolutions of VGG16 features[0:30] with their four max-pools, and the five
+ * normalise / difference / lin / spatial-mean heads, fp32 on the exact-fp32 MFMA, with a backward to the images only.  The
+ * full semantics are spelled out at the top of csrc/lpips.hip (recalled from the public packages: neither was available to
+ * check against).  Feature maps are channels-last (H, W, C); images are (3, H, W) with a channel stride and a row stride
+ * in floats (the pixels of a row are adjacent), so a crop of a larger image is read in place.
+ *
+ * GsLpipsArgs: H, W in GS_LPIPS_MIN_SIZE..GS_LPIPS_MAX_SIZE; normalize != 0: the images are in [0, 1]; need_grad0 / need_grad1:
+ *   whether the forward saves what the backward to in0 / in1 needs (an image without it saves nothing); in0, in1 with
+ *   their strides cs* (>= 1) and rs* (>= W); `packed`: what gs_lpips_pack_weights wrote (16-byte aligned).  The parameter
+ *   addresses weight[l] (Cout, Cin, 3, 3), bias[l] (Cout), lin[k] (C_k), shift (3), scale (3) -- the last two may be NULL: the
+ *   defaults -- are read by gs_lpips_pack_weights only and travel to its kernel by value.
+ * gs_lpips_pack_weights: the weights repacked for both directions into `packed` (gs_lpips_packed_bytes), once.
+ * gs_lpips_workspace_bytes(H, W, need_grad0, need_grad1, which): which = GS_LPIPS_WS_FORWARD the forward's transient
+ *   workspace, GS_LPIPS_WS_SAVED what the forward saves for the backward (0 bytes when neither image needs a gradient),
+ *   GS_LPIPS_WS_BACKWARD the backward's transient workspace.
+ * gs_lpips_forward: loss[1] and, unless NULL, per_tap[GS_LPIPS_TAPS] (their sum in order is the loss).
+ * gs_lpips_backward: d_in0 / d_in1 (3, H, W) contiguous, NULL = not wanted (allowed only for an image whose need_grad is
+ *   set); dL_dloss a device scalar, NULL = 1; `saved` as the forward with the same flags left it.
+ * gs_lpips_conv: ONE layer (0..GS_LPIPS_LAYERS - 1) of the packed weights on caller-given maps.  backward == 0: out (H, W,
+ *   Cout) = relu(conv(in) + bias); layer 0 reads `in` as an image through in_cs / in_rs and transforms it (`normalize`),
+ *   every other layer reads (H, W, Cin) and ignores the strides.  backward != 0: out (H, W, Cin) = the backward-data
+ *   convolution of `in` (H, W, Cout) masked by `mask` > 0 ((H, W, Cout), the layer's saved output); layer 0 writes the image
+ *   gradient (3, H, W), times the transform's factor.  Any H, W >= 1.
+ * gs_lpips_pool: backward == 0: out (H / 2, W / 2, C) = the 2x2 max-pool of in (H, W, C); != 0: out (H, W, C) = g + the
+ *   gradient dp (H / 2, W / 2, C) routed to the first maximum of every window of `in`.  C a multiple of 4.
+ * Every map, `packed`, `saved` and the workspaces are 16-byte aligned.  No atomics, no memsets: bitwise reproducible.
+ * GS_E_BAD_ARG (before any HIP call): a NULL args or required pointer, a size outside the range, a stride below its
+ *   minimum, a misaligned pointer, a gradient asked for an image whose need_grad is 0.  GS_E_WORKSPACE: a buffer smaller
+ *   than gs_lpips_workspace_bytes says. ---- */
+#define GS_LPIPS_LAYERS 13
+#define GS_LPIPS_TAPS 5
+#define GS_LPIPS_MIN_SIZE 16
+#define GS_LPIPS_MAX_SIZE 2048
+#define GS_LPIPS_WS_FORWARD 0
+#define GS_LPIPS_WS_SAVED 1
+#define GS_LPIPS_WS_BACKWARD 2
+typedef struct GsLpipsArgs {
+    int32_t H, W, normalize, need_grad0, need_grad1;
+    int64_t cs0, rs0, cs1, rs1;
+    const float *in0, *in1, *packed;
+    const float* weight[GS_LPIPS_LAYERS];
+    const float* bias[GS_LPIPS_LAYERS];
+    const float* lin[GS_LPIPS_TAPS];
+    const float *shift, *scale;
+} GsLpipsArgs;
+int gs_lpips_packed_bytes(size_t* out);
+int gs_lpips_pack_weights(const GsLpipsArgs* a, void* packed, size_t packed_bytes, void* stream);
+int gs_lpips_workspace_bytes(int32_t H, int32_t W, int32_t need_grad0, int32_t need_grad1, int32_t which, size_t* out);
+int gs_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, void* saved, size_t saved_bytes, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int gs_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const void* saved,
+                      size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gs_lpips_conv(const float* packed, int32_t layer, int32_t backward, int32_t normalize, int32_t H, int32_t W, const float* in,
+                  int64_t in_cs, int64_t in_rs, const float* mask, float* out, void* stream);
+int gs_lpips_pool(int32_t backward, int32_t H, int32_t W, int32_t C, const float* in, const float* g, const float* dp, float* out,
+                  void* stream);
 
 /* ---- introspection for parity tests: device pointers INTO the opaque state buffers.  `field`: one of the enums below
  * (the numbers are part of the ABI; a number past a state's range, or an image field the state does not have, is
