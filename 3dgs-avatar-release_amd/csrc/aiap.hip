@@ -31,6 +31,7 @@
 // entries l, l + 64, ... and the DPP ladder adds the lanes.  No atomics anywhere: the same input gives the same bits.
 // Rows are read with 4-byte loads (a D = 3 row is 12 bytes: any 4-byte-aligned base is accepted).
 #include "common.h"
+#include "boundary.h"
 
 #define AIAP_THREADS 256
 #define AIAP_HEAVY 64  // incoming pairs above which the wave takes a row over
@@ -73,7 +74,7 @@ static inline size_t aiap_carve(int N, int K, char* base, AiapWs* w) {
     }
     return o;
 }
-size_t aiap_workspace_bytes(int N, int K) { return aiap_carve(N, K, nullptr, nullptr); }
+static size_t aiap_workspace_bytes(int N, int K) { return aiap_carve(N, K, nullptr, nullptr); }
 
 struct AiapSet {
     const float* xc;
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_offsets_kernel(int N, long 
     }
 }
 
-int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, void* workspace, hipStream_t s) {
+static int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, void* workspace, hipStream_t s) {
     AiapWs w;
     aiap_carve(N, K, (char*)workspace, &w);
     const long long M = (long long)N * (K - 1);
@@ -364,8 +365,8 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_bwd_kernel(int N, int K, co
     }
 }
 
-int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
-                         hipStream_t s) {
+static int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
+                                hipStream_t s) {
     AiapWs w;
     aiap_carve(N, K, (char*)const_cast<void*>(workspace), &w);
     const long long M = (long long)N * (K - 1);
@@ -387,3 +388,39 @@ int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const G
     GS_LAUNCH_CHECK("aiap_bwd", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+// M = N (K - 1) pairs stay below 2^31 (the sort and the adjacency index 32-bit words)
+static bool aiap_shape_ok(int32_t N, int32_t K, int32_t n_sets) {
+    return N >= 1 && K >= 2 && K <= 8 && (n_sets == 1 || n_sets == 2) && (int64_t)N * (K - 1) < ((int64_t)1 << 31);
+}
+static bool aiap_sets_ok(int32_t n_sets, const GsAiapSet* sets, bool forward) {
+    if (!sets) return false;
+    for (int k = 0; k < n_sets; k++) {
+        const GsAiapSet& s = sets[k];
+        if ((s.D != 3 && s.D != 6) || !s.xc || !s.xd || (forward && !s.loss)) return false;
+    }
+    return true;
+}
+int gs_aiap_workspace_bytes(int32_t N, int32_t K, int32_t n_sets, size_t* out) {
+    if (!out || !aiap_shape_ok(N, K, n_sets)) return GS_E_BAD_ARG;
+    *out = aiap_workspace_bytes(N, K);
+    return GS_OK;
+}
+int gs_aiap_forward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, true)) return GS_E_BAD_ARG;
+    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
+    return launch_aiap_forward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
+}
+int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets,
+                     const void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, false)) return GS_E_BAD_ARG;
+    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
+    return launch_aiap_backward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,6 +1,8 @@
-// capi.hip -- the extern "C" boundary declared in include/gsplat_mi355.h.  Host-side sequencing of
-// the stages; no device allocation, no implicit synchronisation (except in debug mode).
+// capi.hip -- the frame path's part of the extern "C" boundary declared in include/gsplat_mi355.h (every other module's
+// entry points close its own .hip), and what the whole boundary shares: error state, tuning switches, the stage timer, the
+// capture query.  Host-side sequencing of the stages; no device allocation, no implicit synchronisation (except in debug mode).
 #include "common.h"
+#include "boundary.h"
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
@@ -82,7 +84,7 @@ struct ProfState {
 // process-wide (autograd runs the backward on its own host thread), guarded by a mutex
 static ProfState g_prof;
 static std::mutex g_prof_mu;
-static bool profiling_on() { return g_prof.on; }
+bool profiling_on() { return g_prof.on; }
 void gs_prof_begin(const char* stage, hipStream_t s) {
     if (!g_prof.on) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -117,7 +119,7 @@ static int validate(const GsFwdArgs* a) {
         if (a->M > 16) return GS_E_BAD_ARG;  // degree <= 3: the per-Gaussian backward stages 3 M floats per thread in LDS
     }
     // quaternions are read (and their gradients written) as float4
-    if (a->rotations && ((uintptr_t)a->rotations & 15u)) return GS_E_BAD_ARG;
+    if (!aligned(a->rotations, 16)) return GS_E_BAD_ARG;
     if ((a->W + TILE - 1) / TILE > 0xFFFF || (a->H + TILE - 1) / TILE > 0xFFFF) return GS_E_TOO_LARGE;
     return GS_OK;
 }
@@ -129,7 +131,7 @@ static int validate(const GsFwdArgs* a) {
 // STORES into pinned host memory (GsFwdArgs.frame_stats).  None of that is needed under capture: the library now asks
 // hipStreamIsCapturing at every entry point, enqueues KERNEL NODES ONLY on a capturing stream (zero_words_kernel instead
 // of memset nodes), and answers GS_E_CAPTURE -- before enqueuing anything -- to every call that would need more.
-static bool stream_is_capturing(void* stream) {
+bool stream_is_capturing(void* stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     const hipError_t e = hipStreamIsCapturing((hipStream_t)stream, &st);
     if (e != hipSuccess) {
@@ -139,12 +141,7 @@ static bool stream_is_capturing(void* stream) {
     }
     return st != hipStreamCaptureStatusNone;
 }
-// capture-safe entry points: refuse debug mode (it synchronises) and the stage timer (event nodes) under capture
-#define GS_CAPTURE_OK_IF(stream, cond)                                           \
-    do {                                                                         \
-        if (stream_is_capturing(stream) && (!(cond) || profiling_on())) return GS_E_CAPTURE; \
-    } while (0)
-#define GS_NO_CAPTURE(stream) GS_CAPTURE_OK_IF(stream, false)
+// (GS_CAPTURE_OK_IF / GS_NO_CAPTURE, what every entry point asks with: boundary.h)
 
 __global__ void zero_words_kernel(uint32_t* __restrict__ p, size_t words) {
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < words; k += (size_t)gridDim.x * blockDim.x) p[k] = 0u;
@@ -548,7 +545,7 @@ static int backward_impl(const GsFwdArgs* a, const int32_t* radii, const void* g
             return GS_E_BAD_ARG;
         if (a->P > 0 && a->shs && !gr->dL_dsh) return GS_E_BAD_ARG;
         if (a->P > 0 && a->scales && (!gr->dL_dscales || !gr->dL_drotations)) return GS_E_BAD_ARG;
-        if (gr->dL_drotations && ((uintptr_t)gr->dL_drotations & 15u)) return GS_E_BAD_ARG;  // written as float4
+        if (!aligned(gr->dL_drotations, 16)) return GS_E_BAD_ARG;  // written as float4
         return GS_OK;
     });
     if (rc != GS_OK) return rc;
@@ -620,729 +617,6 @@ int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, co
     if (P < 0 || !viewmatrix || (P > 0 && (!means3D || !present))) return GS_E_BAD_ARG;
     if (P == 0) return GS_OK;
     return launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream);
-}
-
-int knn_workspace_bytes(int32_t P, size_t* out) {
-    if (!out || P < 0) return GS_E_BAD_ARG;
-    *out = knn_ws_bytes(P);
-    return GS_OK;
-}
-int knn_dist2(int32_t P, const float* points, float* mean_d2, void* workspace, size_t workspace_bytes, void* stream) {
-    GS_NO_CAPTURE(stream);  // (the sorts clear their tables with memset nodes: untested under replay)
-    if (P < 0 || (P > 0 && (!points || !mean_d2 || !workspace))) return GS_E_BAD_ARG;
-    if (P == 0) return GS_OK;
-    return launch_knn(P, points, mean_d2, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int gs_build_covariance(int32_t N, const float* scaling, float scaling_modifier, const float* rotation, int32_t rotation_is_matrix,
-                        float* cov6, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (N > 0 && (!scaling || !rotation || !cov6))) return GS_E_BAD_ARG;
-    if (!rotation_is_matrix && ((uintptr_t)rotation & 15u)) return GS_E_BAD_ARG;  // quaternions are read as float4
-    if (N == 0) return GS_OK;
-    return launch_build_cov(N, scaling, scaling_modifier, rotation, rotation_is_matrix ? 1 : 0, cov6, (hipStream_t)stream);
-}
-int gs_build_covariance_backward(int32_t N, const float* scaling, float scaling_modifier, const float* rotation,
-                                 int32_t rotation_is_matrix, const float* dL_dcov6, float* dL_dscaling, float* dL_drotation,
-                                 void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (N > 0 && (!scaling || !rotation || !dL_dcov6 || !dL_dscaling || !dL_drotation))) return GS_E_BAD_ARG;
-    if (!rotation_is_matrix && (((uintptr_t)rotation | (uintptr_t)dL_drotation) & 15u)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    return launch_build_cov_bwd(N, scaling, scaling_modifier, rotation, rotation_is_matrix ? 1 : 0, dL_dcov6, dL_dscaling,
-                                dL_drotation, (hipStream_t)stream);
-}
-int gs_sh2rgb(int32_t N, int32_t sh_degree, int32_t M, const float* shs, const float* xyz, const float* campos,
-              const float* fwd_rotation, const float* view_noise_host, float* colors, uint8_t* clamped, void* stream) {
-    GS_CAPTURE_OK_IF(stream, view_noise_host == nullptr);  // (a host matrix would be baked into the graph)
-    if (N < 0 || sh_degree < 0 || sh_degree > 3 || M < (sh_degree + 1) * (sh_degree + 1) || M > 16) return GS_E_BAD_ARG;
-    if (N > 0 && (!shs || !xyz || !campos || !colors || !clamped)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    return launch_sh2rgb(N, sh_degree, M, shs, xyz, campos, fwd_rotation, view_noise_host, colors, clamped, (hipStream_t)stream);
-}
-int gs_sh2rgb_backward(int32_t N, int32_t sh_degree, int32_t M, const float* shs, const float* xyz, const float* campos,
-                       const float* fwd_rotation, const float* view_noise_host, const uint8_t* clamped,
-                       const float* dL_dcolors, float* dL_dshs, float* dL_dxyz, void* stream) {
-    GS_CAPTURE_OK_IF(stream, view_noise_host == nullptr);
-    if (N < 0 || sh_degree < 0 || sh_degree > 3 || M < (sh_degree + 1) * (sh_degree + 1) || M > 16) return GS_E_BAD_ARG;
-    if (N > 0 && (!shs || !xyz || !campos || !clamped || !dL_dcolors || !dL_dshs || !dL_dxyz)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    return launch_sh2rgb_bwd(N, sh_degree, M, shs, xyz, campos, fwd_rotation, view_noise_host, clamped, dL_dcolors, dL_dshs,
-                             dL_dxyz, (hipStream_t)stream);
-}
-
-int gs_l1_loss_workspace_bytes(int64_t n, size_t* out) {
-    if (!out || n < 0) return GS_E_BAD_ARG;
-    *out = l1_ws_bytes(n);
-    return GS_OK;
-}
-int gs_l1_loss(int64_t n, const float* x, const float* y, float* loss, float* dL_dx, void* workspace, size_t workspace_bytes,
-               void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (n <= 0 || !x || !y || !loss || !dL_dx || !workspace) return GS_E_BAD_ARG;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dL_dx) & 15u) return GS_E_BAD_ARG;  // float4 accesses
-    if (workspace_bytes < l1_ws_bytes(n)) return GS_E_WORKSPACE;
-    return launch_l1_loss(x, y, n, loss, dL_dx, (float*)workspace, (hipStream_t)stream);
-}
-
-int gs_bce_loss(int64_t n, const float* x, const float* y, float* loss, float* dL_dx, void* workspace, size_t workspace_bytes,
-                void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (n <= 0 || !x || !y || !loss || !dL_dx || !workspace) return GS_E_BAD_ARG;
-    if (workspace_bytes < l1_ws_bytes(n)) return GS_E_WORKSPACE;
-    return launch_bce_loss(x, y, n, loss, dL_dx, (float*)workspace, (hipStream_t)stream);
-}
-
-int gs_ssim_workspace_bytes(int32_t C, int32_t H, int32_t W, size_t* out) {
-    if (!out || C <= 0 || H <= 0 || W <= 0) return GS_E_BAD_ARG;
-    *out = ssim_ws_bytes(C, H, W);
-    return GS_OK;
-}
-int gs_ssim_forward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_out, float* dm_dmu1,
-                    float* dm_dsigma1_sq, float* dm_dsigma12, void* workspace, size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !ssim_out || !workspace) return GS_E_BAD_ARG;
-    if ((dm_dmu1 != nullptr) != (dm_dsigma1_sq != nullptr) || (dm_dmu1 != nullptr) != (dm_dsigma12 != nullptr)) return GS_E_BAD_ARG;
-    if (workspace_bytes < ssim_ws_bytes(C, H, W)) return GS_E_WORKSPACE;
-    return launch_ssim_forward(C, H, W, img1, img2, ssim_out, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, (float*)workspace,
-                               (hipStream_t)stream);
-}
-int gs_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, const float* dm_dmu1,
-                     const float* dm_dsigma1_sq, const float* dm_dsigma12, const float* dL_dssim, float* dL_dimg1,
-                     void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dssim || !dL_dimg1)
-        return GS_E_BAD_ARG;
-    return launch_ssim_backward(C, H, W, img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dssim, dL_dimg1,
-                                (hipStream_t)stream);
-}
-
-int gs_densify_stats(int32_t N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
-                     float* xyz_gradient_accum, float* denom, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (N > 0 && (!radii || !viewspace_grad || !max_radii2D || !xyz_gradient_accum || !denom))) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    return launch_densify_stats(N, radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, (hipStream_t)stream);
-}
-int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step,
-                 void* stream) {
-    GS_NO_CAPTURE(stream);  // (the step number is a host scalar: a replay would repeat the captured step's bias correction)
-    if (n_tensors < 0 || n_tensors > GS_ADAM_MAX_TENSORS || (n_tensors > 0 && !tensors) || step < 1) return GS_E_BAD_ARG;
-    for (int k = 0; k < n_tensors; k++) {
-        const GsAdamTensor& t = tensors[k];
-        if (t.n < 0 || (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) return GS_E_BAD_ARG;
-    }
-    if (n_tensors == 0) return GS_OK;
-    return launch_adam(n_tensors, tensors, beta1, beta2, eps, step, (hipStream_t)stream);
-}
-
-// ---- the converter's optimizer step (optim.hip): every argument check comes before the first HIP call
-#define GS_OPTIM_MAX_N ((int64_t)1 << 41)  // chunks of 2048 elements are counted in an int
-static int grad_tensors_ok(int32_t n_tensors, const GsGradTensor* tensors) {
-    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
-    for (int k = 0; k < n_tensors; k++)
-        if (tensors[k].n < 0 || (tensors[k].n > 0 && !tensors[k].grad)) return GS_E_BAD_ARG;
-    for (int k = 0; k < n_tensors; k++)
-        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
-    return GS_OK;
-}
-int gs_grad_norm_workspace_bytes(int32_t n_tensors, const GsGradTensor* tensors, size_t* out) {
-    if (!out) return GS_E_BAD_ARG;
-    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
-    *out = grad_norm_workspace_bytes(n_tensors, tensors);
-    return GS_OK;
-}
-int gs_grad_norm(int32_t n_tensors, const GsGradTensor* tensors, float max_norm, float* out, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-    if (!out || !workspace || !(max_norm >= 0.f)) return GS_E_BAD_ARG;
-    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
-    if (workspace_bytes < grad_norm_workspace_bytes(n_tensors, tensors)) return GS_E_WORKSPACE;
-    if (n_tensors == 0) return GS_OK;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_grad_norm(n_tensors, tensors, max_norm, out, (float*)workspace, (hipStream_t)stream);
-}
-int gs_grad_scale(int32_t n_tensors, const GsGradTensor* tensors, const float* clip_coef, void* stream) {
-    if (!clip_coef) return GS_E_BAD_ARG;
-    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
-    if (n_tensors == 0) return GS_OK;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_grad_scale(n_tensors, tensors, clip_coef, (hipStream_t)stream);
-}
-int gs_adam_step_ex(int32_t n_tensors, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
-                    const float* clip_coef, void* stream) {
-    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
-    bool host_step = false;
-    for (int k = 0; k < n_tensors; k++) {
-        const GsAdamTensorEx& t = tensors[k];
-        if (t.n < 0 || (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) return GS_E_BAD_ARG;
-        if (!t.step) host_step = true;
-    }
-    if (host_step && step < 1) return GS_E_BAD_ARG;
-    for (int k = 0; k < n_tensors; k++)
-        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
-    if (n_tensors == 0) return GS_OK;
-    // (a host step number under capture: a replay would repeat the captured step's bias correction)
-    GS_CAPTURE_OK_IF(stream, !host_step);
-    return launch_adam_ex(n_tensors, tensors, beta1, beta2, eps, host_step ? step : 0, clip_coef, (hipStream_t)stream);
-}
-
-// ---- densification cycle (densify.hip).  N < 2^30: the map packs a source index and a two-bit slot into 32 bits, and
-// N' <= 2 N stays an int32
-#define GS_DENSIFY_MAX_N (1 << 30)
-int gs_densify_workspace_bytes(int32_t N, size_t* out) {
-    if (!out || N < 0 || N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
-    *out = densify_workspace_bytes(N);
-    return GS_OK;
-}
-int gs_densify_plan(const GsDensifyPlan* p, void* workspace, size_t workspace_bytes, int32_t* count_host_pinned,
-                    void* stream) {
-    GS_CAPTURE_OK_IF(stream, count_host_pinned == nullptr);
-    if (!p || !workspace || p->N < 0 || p->N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
-    if (p->N > 0 && !p->prune_mask && (!p->scaling || !p->opacity || !p->grad_accum || !p->denom)) return GS_E_BAD_ARG;
-    if (workspace_bytes < densify_workspace_bytes(p->N)) return GS_E_WORKSPACE;
-    return launch_densify_plan(*p, workspace, count_host_pinned, (hipStream_t)stream);
-}
-int gs_densify_apply(int32_t N, int32_t N_new, const void* workspace, size_t workspace_bytes, int32_t n_tensors,
-                     const GsDensifyTensor* tensors, const float* scaling, const float* rotation, const float* noise,
-                     void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || N >= GS_DENSIFY_MAX_N || N_new < 0 || N_new > 2 * N || !workspace || n_tensors < 0 ||
-        n_tensors > GS_DENSIFY_MAX_TENSORS || (n_tensors > 0 && !tensors))
-        return GS_E_BAD_ARG;
-    if (workspace_bytes < densify_workspace_bytes(N)) return GS_E_WORKSPACE;
-    for (int k = 0; k < n_tensors; k++) {
-        const GsDensifyTensor& t = tensors[k];
-        if (t.width <= 0 || t.kind < GS_DENSIFY_COPY || t.kind > GS_DENSIFY_CHILD_SCALING) return GS_E_BAD_ARG;
-        if (N_new > 0 && (!t.dst || (t.kind != GS_DENSIFY_ZERO && !t.src))) return GS_E_BAD_ARG;
-        if ((t.kind == GS_DENSIFY_CHILD_POSITION || t.kind == GS_DENSIFY_CHILD_SCALING) && t.width != 3) return GS_E_BAD_ARG;
-        if (t.kind == GS_DENSIFY_CHILD_POSITION && N_new > 0 && (!scaling || !rotation || !noise)) return GS_E_BAD_ARG;
-    }
-    if (N_new == 0 || n_tensors == 0) return GS_OK;
-    return launch_densify_apply(N, N_new, workspace, n_tensors, tensors, scaling, rotation, noise, (hipStream_t)stream);
-}
-int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, float* exp_avg, float* exp_avg_sq,
-                     void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (N > 0 && (!opacity_in || !opacity_out))) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    return launch_reset_opacity(N, opacity_in, opacity_out, exp_avg, exp_avg_sq, (hipStream_t)stream);
-}
-
-// ---- AIAP regularisers (aiap.hip).  M = N (K - 1) pairs stay below 2^31 (the sort and the adjacency index 32-bit words)
-static bool aiap_shape_ok(int32_t N, int32_t K, int32_t n_sets) {
-    return N >= 1 && K >= 2 && K <= 8 && (n_sets == 1 || n_sets == 2) && (int64_t)N * (K - 1) < ((int64_t)1 << 31);
-}
-static bool aiap_sets_ok(int32_t n_sets, const GsAiapSet* sets, bool forward) {
-    if (!sets) return false;
-    for (int k = 0; k < n_sets; k++) {
-        const GsAiapSet& s = sets[k];
-        if ((s.D != 3 && s.D != 6) || !s.xc || !s.xd || (forward && !s.loss)) return false;
-    }
-    return true;
-}
-int gs_aiap_workspace_bytes(int32_t N, int32_t K, int32_t n_sets, size_t* out) {
-    if (!out || !aiap_shape_ok(N, K, n_sets)) return GS_E_BAD_ARG;
-    *out = aiap_workspace_bytes(N, K);
-    return GS_OK;
-}
-int gs_aiap_forward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, true)) return GS_E_BAD_ARG;
-    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
-    return launch_aiap_forward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
-}
-int gs_aiap_backward(int32_t N, int32_t K, const int64_t* idx, int32_t n_sets, const GsAiapSet* sets,
-                     const void* workspace, size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!aiap_shape_ok(N, K, n_sets) || !idx || !workspace || !aiap_sets_ok(n_sets, sets, false)) return GS_E_BAD_ARG;
-    if (workspace_bytes < aiap_workspace_bytes(N, K)) return GS_E_WORKSPACE;
-    return launch_aiap_backward(N, K, (const long long*)idx, n_sets, sets, workspace, (hipStream_t)stream);
-}
-
-// ---- hash-grid encoding (hashgrid.hip)
-static bool hg_aligned(const void* p, int F) { return p == nullptr || ((uintptr_t)p % (uintptr_t)(4 * (F < 4 ? F : 4))) == 0; }
-int gs_hashgrid_levels(const GsHashGrid* grid, int32_t* offsets, float* scales, int32_t* resolutions, int32_t* n_params) {
-    if (!grid) return GS_E_BAD_ARG;
-    HgTable t;
-    const int rc = hashgrid_table(grid, &t);
-    if (rc != GS_OK) return rc;
-    for (int l = 0; l <= t.L; l++) {
-        if (offsets) offsets[l] = (int32_t)t.off[l];
-        if (l == t.L) break;
-        if (scales) scales[l] = t.scale[l];
-        if (resolutions) resolutions[l] = (int32_t)t.res[l];
-    }
-    if (n_params) *n_params = (int32_t)(t.off[t.L] * (uint32_t)t.F);
-    return GS_OK;
-}
-// the sort numbers the 8 L N (point, level, corner) pairs with 32-bit words
-static bool hg_pairs_fit(const HgTable& t, int32_t N) { return (int64_t)8 * t.L * N < ((int64_t)1 << 31); }
-int gs_hashgrid_workspace_bytes(const GsHashGrid* grid, int32_t N, size_t* out) {
-    if (!grid || !out || N < 0) return GS_E_BAD_ARG;
-    HgTable t;
-    const int rc = hashgrid_table(grid, &t);
-    if (rc != GS_OK) return rc;
-    if (!hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
-    *out = hashgrid_workspace_bytes(t, N);
-    return GS_OK;
-}
-int gs_hashgrid_forward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, float* out, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!grid || N < 0) return GS_E_BAD_ARG;
-    HgTable t;
-    const int rc = hashgrid_table(grid, &t);
-    if (rc != GS_OK) return rc;
-    if ((int64_t)N * t.L >= ((int64_t)1 << 31)) return GS_E_TOO_LARGE;
-    if (N == 0 || !out) return GS_OK;
-    if (!x || !params || !hg_aligned(params, t.F) || !hg_aligned(out, t.F) || !hg_aligned(x, 1)) return GS_E_BAD_ARG;
-    return launch_hashgrid_forward(t, N, x, params, out, (hipStream_t)stream);
-}
-int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, const float* dL_dout,
-                         float* dL_dx, float* dL_dparams, void* workspace, size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!grid || N < 0) return GS_E_BAD_ARG;
-    HgTable t;
-    const int rc = hashgrid_table(grid, &t);
-    if (rc != GS_OK) return rc;
-    if (dL_dparams && !hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
-    if (!dL_dparams && (N == 0 || !dL_dx)) return GS_OK;
-    if (N > 0 && (!x || !dL_dout || (dL_dx && !params))) return GS_E_BAD_ARG;
-    if (!hg_aligned(params, t.F) || !hg_aligned(dL_dout, t.F) || !hg_aligned(dL_dparams, t.F) || !hg_aligned(x, 1) ||
-        !hg_aligned(dL_dx, 1))
-        return GS_E_BAD_ARG;
-    if (dL_dparams) {
-        if (!workspace) return GS_E_BAD_ARG;
-        if (workspace_bytes < hashgrid_workspace_bytes(t, N)) return GS_E_WORKSPACE;
-    }
-    return launch_hashgrid_backward(t, N, x, params, dL_dout, N > 0 ? dL_dx : nullptr, dL_dparams, workspace,
-                                    (hipStream_t)stream);
-}
-
-// ---- linear blend skinning (skinning.hip)
-static bool skin_a16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static bool skin_a4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-static bool skin_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX || kind == GS_SKIN_WEIGHTS; }
-int gs_skin_weights_forward(int32_t N, int32_t kind, const float* logits, float* weights, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!logits || !weights || !skin_a16(logits) || !skin_a16(weights)) return GS_E_BAD_ARG;
-    return launch_skin_weights_forward(N, kind, logits, weights, (hipStream_t)stream);
-}
-int gs_skin_weights_backward(int32_t N, int32_t kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
-                             void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!logits || !dL_dweights || !dL_dlogits || !skin_a16(logits) || !skin_a16(dL_dweights) || !skin_a16(dL_dlogits))
-        return GS_E_BAD_ARG;
-    return launch_skin_weights_backward(N, kind, logits, dL_dweights, dL_dlogits, (hipStream_t)stream);
-}
-int gs_skinning_workspace_bytes(int32_t N, size_t* out) {
-    if (!out || N < 0) return GS_E_BAD_ARG;
-    *out = skinning_workspace_bytes(N);
-    return GS_OK;
-}
-int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
-                        float* xyz_out, float* rotation_out, float* T_fwd, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!w || !tfs || !xyz || !rotation || !xyz_out || !rotation_out || !T_fwd) return GS_E_BAD_ARG;
-    if (!skin_a16(w) || !skin_a16(tfs) || !skin_a16(rotation) || !skin_a16(xyz_out) || !skin_a16(rotation_out) ||
-        !skin_a16(T_fwd) || !skin_a4(xyz))
-        return GS_E_BAD_ARG;
-    return launch_skinning_forward(N, kind, w, tfs, xyz, rotation, xyz_out, rotation_out, T_fwd, (hipStream_t)stream);
-}
-int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
-                         const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
-                         float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!w || !tfs || !xyz || !rotation) return GS_E_BAD_ARG;
-    if (!skin_a16(w) || !skin_a16(tfs) || !skin_a16(rotation) || !skin_a4(xyz) || !skin_a4(dL_dxyz_out) ||
-        !skin_a4(dL_drotation_out) || !skin_a16(dL_dw) || !skin_a4(dL_dtfs) || !skin_a4(dL_dxyz) || !skin_a16(dL_drotation))
-        return GS_E_BAD_ARG;
-    if (dL_dtfs) {
-        if (!workspace || !skin_a16(workspace)) return GS_E_BAD_ARG;
-        if (workspace_bytes < skinning_workspace_bytes(N)) return GS_E_WORKSPACE;
-    }
-    if (!dL_dw && !dL_dtfs && !dL_dxyz && !dL_drotation) return GS_OK;
-    return launch_skinning_backward(N, kind, w, tfs, xyz, rotation, dL_dxyz_out, dL_drotation_out, dL_dw, dL_dtfs, dL_dxyz,
-                                    dL_drotation, workspace, (hipStream_t)stream);
-}
-
-// ---- the skinning regulariser (skinloss.hip)
-static bool skin_loss_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX; }
-int gs_mesh_sample(int32_t n, int32_t V, int32_t F, const float* verts, const int32_t* faces, const float* cdf,
-                   const float* vweights, const float* aabb_min, const float* aabb_inv_extent, const float* draws,
-                   float* points_norm, float* target, int32_t* face, float* bary, float* points, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (n < 0 || V < 1 || F < 1) return GS_E_BAD_ARG;
-    if (!verts || !faces || !cdf || !vweights || !aabb_min || !aabb_inv_extent) return GS_E_BAD_ARG;
-    if (!skin_a4(verts) || !skin_a4(faces) || !skin_a4(cdf) || !skin_a16(vweights) || !skin_a4(aabb_min) ||
-        !skin_a4(aabb_inv_extent))
-        return GS_E_BAD_ARG;
-    if (n == 0) return GS_OK;
-    if (!draws || !points_norm || !target) return GS_E_BAD_ARG;
-    if (!skin_a4(draws) || !skin_a16(points_norm) || !skin_a16(target) || !skin_a4(face) || !skin_a16(bary) || !skin_a16(points))
-        return GS_E_BAD_ARG;
-    return launch_mesh_sample(n, V, F, verts, faces, cdf, vweights, aabb_min, aabb_inv_extent, draws, points_norm, target, face,
-                              bary, points, (hipStream_t)stream);
-}
-int gs_skin_loss_workspace_bytes(int32_t n, size_t* out) {
-    if (!out || n < 0) return GS_E_BAD_ARG;
-    *out = skin_loss_workspace_bytes(n);
-    return GS_OK;
-}
-int gs_skin_loss_forward(int32_t n, int32_t kind, const float* logits, const float* target, float* loss, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
-    if (n == 0) return GS_OK;
-    if (!logits || !target || !loss || !workspace) return GS_E_BAD_ARG;
-    if (!skin_a16(logits) || !skin_a16(target) || !skin_a4(loss) || !skin_a16(workspace)) return GS_E_BAD_ARG;
-    if (workspace_bytes < skin_loss_workspace_bytes(n)) return GS_E_WORKSPACE;
-    return launch_skin_loss_forward(n, kind, logits, target, loss, workspace, (hipStream_t)stream);
-}
-int gs_skin_loss_backward(int32_t n, int32_t kind, const float* logits, const float* target, const float* dL_dloss,
-                          float* dL_dlogits, void* stream) {
-    GS_CAPTURE_OK_IF(stream, true);
-    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
-    if (n == 0) return GS_OK;
-    if (!logits || !target || !dL_dloss || !dL_dlogits) return GS_E_BAD_ARG;
-    if (!skin_a16(logits) || !skin_a16(target) || !skin_a4(dL_dloss) || !skin_a16(dL_dlogits)) return GS_E_BAD_ARG;
-    return launch_skin_loss_backward(n, kind, logits, target, dL_dloss, dL_dlogits, (hipStream_t)stream);
-}
-
-// ---- SMPL pose correction (pose.hip)
-static bool pose_a4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-static bool pose_req(const void* p) { return p && pose_a4(p); }
-static int pose_validate(const GsPoseArgs* a) {
-    if (!a || a->V < 1 || a->NB < 1 || a->NB > GS_POSE_MAX_BETAS) return GS_E_BAD_ARG;
-    for (int i = 1; i < GS_POSE_BONES; i++)
-        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
-    if (!pose_req(a->J_shapedirs) || !pose_req(a->root_orient) || !pose_req(a->pose_body) || !pose_req(a->pose_hand) ||
-        !pose_a4(a->rots_gt))
-        return GS_E_BAD_ARG;
-    return GS_OK;
-}
-int gs_pose_workspace_bytes(int32_t V, size_t* out) {
-    if (!out || V < 1) return GS_E_BAD_ARG;
-    *out = pose_workspace_bytes(V);
-    return GS_OK;
-}
-int gs_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone_transforms, float* loss_pose, float* state,
-                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = pose_validate(a)) return rc;
-    if (!pose_req(a->v_template) || !pose_req(a->shapedirs) || !pose_req(a->J_template) || !pose_req(a->betas) ||
-        !pose_req(a->trans) || !pose_req(rots) || !pose_req(Jtrs) || !pose_req(bone_transforms) || !pose_req(state) ||
-        !pose_a4(loss_pose) || (a->rots_gt && !loss_pose))
-        return GS_E_BAD_ARG;
-    if (!workspace || ((uintptr_t)workspace & 7u)) return GS_E_BAD_ARG;
-    if (workspace_bytes < pose_workspace_bytes(a->V)) return GS_E_WORKSPACE;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_pose_forward(a, rots, Jtrs, bone_transforms, loss_pose, state, workspace, (hipStream_t)stream);
-}
-int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_drots, const float* dL_dJtrs,
-                     const float* dL_dbone_transforms, const float* dL_dloss_pose, float* dL_dbetas, float* dL_droot_orient,
-                     float* dL_dpose_body, float* dL_dpose_hand, float* dL_dtrans, void* stream) {
-    if (const int rc = pose_validate(a)) return rc;
-    if (!pose_req(state) || !pose_a4(dL_drots) || !pose_a4(dL_dJtrs) || !pose_a4(dL_dbone_transforms) || !pose_a4(dL_dloss_pose) ||
-        !pose_a4(dL_dbetas) || !pose_a4(dL_droot_orient) || !pose_a4(dL_dpose_body) || !pose_a4(dL_dpose_hand) || !pose_a4(dL_dtrans))
-        return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!dL_dbetas && !dL_droot_orient && !dL_dpose_body && !dL_dpose_hand && !dL_dtrans) return GS_OK;
-    return launch_pose_backward(a, state, dL_drots, dL_dJtrs, dL_dbone_transforms, dL_dloss_pose, dL_dbetas, dL_droot_orient,
-                                dL_dpose_body, dL_dpose_hand, dL_dtrans, (hipStream_t)stream);
-}
-
-// ---- the non-rigid deformer around its MLP (nonrigid.hip)
-static bool nr_a16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static int pose_enc_validate(const GsPoseEncArgs* a) {
-    if (!a || a->d < 1 || a->d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
-    for (int i = 1; i < GS_POSE_ENC_JOINTS; i++)
-        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
-    if (!pose_req(a->W0)) return GS_E_BAD_ARG;
-    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
-        if (!pose_req(a->W1[j]) || !pose_req(a->W2[j])) return GS_E_BAD_ARG;
-    return GS_OK;
-}
-int gs_pose_encoder_grad_floats(int32_t d, size_t* out) {
-    if (!out || d < 1 || d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
-    *out = pose_encoder_grad_floats(d);
-    return GS_OK;
-}
-int gs_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, void* stream) {
-    if (const int rc = pose_enc_validate(a)) return rc;
-    if (!pose_req(a->rots) || !pose_req(a->Jtrs) || !pose_req(a->b0) || !pose_req(out) || !pose_req(state)) return GS_E_BAD_ARG;
-    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
-        if (!pose_req(a->b1[j]) || !pose_req(a->b2[j])) return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_pose_encoder_forward(a, out, state, (hipStream_t)stream);
-}
-int gs_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* dL_dout, float* dL_dparams,
-                             float* dL_drots, float* dL_dJtrs, void* stream) {
-    if (const int rc = pose_enc_validate(a)) return rc;
-    if (!pose_req(state) || !pose_req(dL_dout) || !pose_a4(dL_dparams) || !pose_a4(dL_drots) || !pose_a4(dL_dJtrs))
-        return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!dL_dparams && !dL_drots && !dL_dJtrs) return GS_OK;
-    return launch_pose_encoder_backward(a, state, dL_dout, dL_dparams, dL_drots, dL_dJtrs, (hipStream_t)stream);
-}
-static bool nr_shape_ok(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset) {
-    return N >= 0 && D >= 10 && D <= GS_NONRIGID_MAX_D &&
-           (scale_offset == GS_NR_SCALE_LOGIT || scale_offset == GS_NR_SCALE_EXP || scale_offset == GS_NR_SCALE_ZERO) &&
-           (rot_offset == GS_NR_ROT_ADD || rot_offset == GS_NR_ROT_MULT);
-}
-int gs_nonrigid_workspace_bytes(int32_t N, int32_t D, size_t* out) {
-    if (!out || N < 0 || D < 10 || D > GS_NONRIGID_MAX_D) return GS_E_BAD_ARG;
-    *out = nonrigid_workspace_bytes(N, D);
-    return GS_OK;
-}
-int gs_nonrigid_apply_forward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
-                              const float* xyz, const float* scaling, const float* rotation, float* xyz_out,
-                              float* scaling_out, float* rotation_out, float* feature, float* losses, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!deltas || !xyz || !rotation || !xyz_out || !rotation_out || (D > 10 && !feature)) return GS_E_BAD_ARG;
-    if (scale_offset != GS_NR_SCALE_ZERO && (!scaling || !scaling_out)) return GS_E_BAD_ARG;
-    if (scaling_out && !scaling) return GS_E_BAD_ARG;
-    if (!nr_a16(deltas) || !nr_a16(rotation) || !nr_a16(rotation_out) || !nr_a16(feature) || !pose_a4(xyz) || !pose_a4(scaling) ||
-        !pose_a4(xyz_out) || !pose_a4(scaling_out) || !pose_a4(losses))
-        return GS_E_BAD_ARG;
-    if (losses) {
-        if (!workspace || !pose_a4(workspace)) return GS_E_BAD_ARG;
-        if (workspace_bytes < nonrigid_workspace_bytes(N, D)) return GS_E_WORKSPACE;
-    }
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_nonrigid_apply_forward(N, D, scale_offset, rot_offset, deltas, xyz, scaling, rotation, xyz_out, scaling_out,
-                                         rotation_out, D > 10 ? feature : nullptr, losses, workspace, (hipStream_t)stream);
-}
-int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
-                               const float* scaling, const float* rotation, const float* dL_dxyz_out,
-                               const float* dL_dscaling_out, const float* dL_drotation_out, const float* dL_dfeature,
-                               const float* dL_dnr_xyz, const float* dL_dnr_scale, const float* dL_dnr_rot,
-                               float* dL_ddeltas, float* dL_dscaling, float* dL_drotation, void* stream) {
-    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
-    if (N == 0) return GS_OK;
-    if (!deltas || (scale_offset == GS_NR_SCALE_EXP && !scaling) || (rot_offset == GS_NR_ROT_MULT && !rotation)) return GS_E_BAD_ARG;
-    if (!nr_a16(deltas) || !nr_a16(rotation) || !nr_a16(dL_drotation_out) || !nr_a16(dL_dfeature) || !nr_a16(dL_ddeltas) ||
-        !nr_a16(dL_drotation) || !pose_a4(scaling) || !pose_a4(dL_dxyz_out) || !pose_a4(dL_dscaling_out) || !pose_a4(dL_dnr_xyz) ||
-        !pose_a4(dL_dnr_scale) || !pose_a4(dL_dnr_rot) || !pose_a4(dL_dscaling))
-        return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!dL_ddeltas && !dL_dscaling && !dL_drotation) return GS_OK;
-    return launch_nonrigid_apply_backward(N, D, scale_offset, rot_offset, deltas, scaling, rotation, dL_dxyz_out, dL_dscaling_out,
-                                          dL_drotation_out, D > 10 ? dL_dfeature : nullptr, dL_dnr_xyz, dL_dnr_scale, dL_dnr_rot,
-                                          dL_ddeltas, dL_dscaling, dL_drotation, (hipStream_t)stream);
-}
-
-// ---- the input of the ColorMLP texture (texture.hip)
-static int texture_validate(const GsTextureArgs* a) {
-    if (!a || a->N < 0 || a->sh_degree < 0 || a->sh_degree > 4 || a->n_before < 0 || a->n_before > GS_TEXTURE_MAX_BEFORE ||
-        a->n_after < 0 || a->n_after > GS_TEXTURE_MAX_AFTER || a->latent_dim < 0 || a->latent_dim > GS_TEXTURE_MAX_D)
-        return GS_E_BAD_ARG;
-    int64_t sum = (a->sh_degree + 1) * (a->sh_degree + 1) - 1 + a->latent_dim;
-    for (int b = 0; b < a->n_before; b++) {
-        if (a->before_w[b] < 1 || a->before_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
-        sum += a->before_w[b];
-    }
-    for (int b = 0; b < a->n_after; b++) {
-        if (a->after_w[b] < 1 || a->after_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
-        sum += a->after_w[b];
-    }
-    if (a->D < 1 || a->D > GS_TEXTURE_MAX_D || sum != a->D) return GS_E_BAD_ARG;
-    return GS_OK;
-}
-// what the view direction is made of (sh_degree > 0)
-static bool texture_dir_ok(const GsTextureArgs* a) {
-    if (!pose_req(a->xyz) || !pose_req(a->campos) || !pose_a4(a->fwd_transform)) return false;
-    return !a->fwd_transform || (a->rot_row >= 3 && a->rot_stride >= 2 * (int64_t)a->rot_row + 3);
-}
-int gs_texture_workspace_bytes(int32_t N, int32_t D, int32_t latent_dim, size_t* out) {
-    if (!out || N < 0 || D < 1 || D > GS_TEXTURE_MAX_D || latent_dim < 0 || latent_dim > D) return GS_E_BAD_ARG;
-    *out = texture_workspace_bytes(N, D, latent_dim);
-    return GS_OK;
-}
-int gs_texture_input_forward(const GsTextureArgs* a, float* inp, void* stream) {
-    if (const int rc = texture_validate(a)) return rc;
-    if (a->N == 0) return GS_OK;
-    if (!inp || !nr_a16(inp)) return GS_E_BAD_ARG;
-    for (int b = 0; b < a->n_before; b++)
-        if (!a->before[b] || !nr_a16(a->before[b])) return GS_E_BAD_ARG;
-    for (int b = 0; b < a->n_after; b++)
-        if (!a->after[b] || !nr_a16(a->after[b])) return GS_E_BAD_ARG;
-    if (a->latent_dim > 0 && !pose_req(a->latent)) return GS_E_BAD_ARG;
-    if (a->sh_degree > 0 && !texture_dir_ok(a)) return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_texture_input_forward(a, inp, (hipStream_t)stream);
-}
-int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, float* const* dL_dbefore, float* const* dL_dafter,
-                              float* dL_dxyz, float* dL_dlatent, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = texture_validate(a)) return rc;
-    if (a->N == 0) return GS_OK;
-    if (!dL_dinp || !nr_a16(dL_dinp)) return GS_E_BAD_ARG;
-    TxGrads gr = {};
-    bool any = dL_dxyz || dL_dlatent;
-    for (int b = 0; b < a->n_before; b++) {
-        gr.before[b] = dL_dbefore ? dL_dbefore[b] : nullptr;
-        if (!nr_a16(gr.before[b])) return GS_E_BAD_ARG;
-        any = any || gr.before[b];
-    }
-    for (int b = 0; b < a->n_after; b++) {
-        gr.after[b] = dL_dafter ? dL_dafter[b] : nullptr;
-        if (!nr_a16(gr.after[b])) return GS_E_BAD_ARG;
-        any = any || gr.after[b];
-    }
-    if (dL_dxyz && (a->sh_degree == 0 || !pose_a4(dL_dxyz) || !texture_dir_ok(a))) return GS_E_BAD_ARG;
-    if (dL_dlatent) {
-        if (a->latent_dim == 0 || !pose_a4(dL_dlatent) || !workspace || !pose_a4(workspace)) return GS_E_BAD_ARG;
-        if (workspace_bytes < texture_workspace_bytes(a->N, a->D, a->latent_dim)) return GS_E_WORKSPACE;
-    }
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!any) return GS_OK;
-    return launch_texture_input_backward(a, dL_dinp, gr, dL_dxyz, dL_dlatent, workspace, (hipStream_t)stream);
-}
-
-// ---- the fused VanillaCondMLP (mlp.hip)
-static int mlp_validate(const GsMlpArgs* a) {
-    if (!a || a->N < 0 || a->width < 32 || a->width > GS_MLP_MAX_WIDTH || a->width % 32 != 0 || a->n_hidden < 1 ||
-        a->n_hidden > GS_MLP_MAX_HIDDEN || a->dim_in < 1 || a->dim_in > GS_MLP_MAX_IN || a->dim_cond < 0 ||
-        a->dim_cond > GS_MLP_MAX_COND || a->dim_out < 1 || a->dim_out > GS_MLP_MAX_OUT || !(a->slope == a->slope))
-        return GS_E_BAD_ARG;
-    return GS_OK;
-}
-// x, the condition and every layer's parameters
-static bool mlp_inputs_ok(const GsMlpArgs* a) {
-    if (!a->x || !nr_a16(a->x) || (a->dim_cond > 0 && !pose_req(a->cond))) return false;
-    for (int l = 0; l <= a->n_hidden; l++)
-        if (!pose_req(a->W[l]) || !pose_req(a->b[l])) return false;
-    return true;
-}
-int gs_mlp_workspace_bytes(const GsMlpArgs* a, int32_t backward, size_t* out) {
-    if (!out) return GS_E_BAD_ARG;
-    if (const int rc = mlp_validate(a)) return rc;
-    *out = mlp_workspace_bytes(a, backward != 0);
-    return GS_OK;
-}
-int gs_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = mlp_validate(a)) return rc;
-    if (a->N == 0) return GS_OK;
-    if (!mlp_inputs_ok(a) || !pose_req(y) || !nr_a16(acts)) return GS_E_BAD_ARG;
-    if (a->dim_cond > 0) {
-        if (!pose_req(workspace)) return GS_E_BAD_ARG;
-        if (workspace_bytes < mlp_workspace_bytes(a, 0)) return GS_E_WORKSPACE;
-    }
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_mlp_forward(a, y, acts, workspace, (hipStream_t)stream);
-}
-int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-    if (const int rc = mlp_validate(a)) return rc;
-    if (a->N == 0) return GS_OK;
-    if (!mlp_inputs_ok(a) || !acts || !nr_a16(acts) || !dL_dy || !nr_a16(dL_dy) || !pose_a4(a->dx) || !pose_a4(a->dcond))
-        return GS_E_BAD_ARG;
-    if (a->dcond && a->dim_cond == 0) return GS_E_BAD_ARG;
-    bool any = a->dx || a->dcond;
-    for (int l = 0; l <= a->n_hidden; l++) {
-        if (!pose_a4(a->dW[l]) || !pose_a4(a->db[l])) return GS_E_BAD_ARG;
-        any = any || a->dW[l] || a->db[l];
-    }
-    if (any) {
-        if (!workspace || !nr_a16(workspace)) return GS_E_BAD_ARG;
-        if (workspace_bytes < mlp_workspace_bytes(a, 1)) return GS_E_WORKSPACE;
-    }
-    GS_CAPTURE_OK_IF(stream, true);
-    if (!any) return GS_OK;
-    return launch_mlp_backward(a, acts, dL_dy, workspace, (hipStream_t)stream);
-}
-
-// ---- the LPIPS-VGG perceptual loss (lpips.hip)
-static bool lp_a16(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
-static int lpips_validate(const GsLpipsArgs* a) {
-    if (!a || a->H < GS_LPIPS_MIN_SIZE || a->H > GS_LPIPS_MAX_SIZE || a->W < GS_LPIPS_MIN_SIZE || a->W > GS_LPIPS_MAX_SIZE)
-        return GS_E_BAD_ARG;
-    if (!pose_req(a->in0) || !pose_req(a->in1) || !lp_a16(a->packed)) return GS_E_BAD_ARG;
-    if (a->cs0 < 1 || a->cs1 < 1 || a->rs0 < a->W || a->rs1 < a->W) return GS_E_BAD_ARG;
-    return GS_OK;
-}
-int gs_lpips_packed_bytes(size_t* out) {
-    if (!out) return GS_E_BAD_ARG;
-    *out = lpips_packed_bytes();
-    return GS_OK;
-}
-int gs_lpips_pack_weights(const GsLpipsArgs* a, void* packed, size_t packed_bytes, void* stream) {
-    if (!a || !lp_a16(packed) || !pose_a4(a->shift) || !pose_a4(a->scale)) return GS_E_BAD_ARG;
-    for (int l = 0; l < GS_LPIPS_LAYERS; l++)
-        if (!pose_req(a->weight[l]) || !pose_req(a->bias[l])) return GS_E_BAD_ARG;
-    for (int k = 0; k < GS_LPIPS_TAPS; k++)
-        if (!pose_req(a->lin[k])) return GS_E_BAD_ARG;
-    if (packed_bytes < lpips_packed_bytes()) return GS_E_WORKSPACE;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_lpips_pack(a, (float*)packed, (hipStream_t)stream);
-}
-int gs_lpips_workspace_bytes(int32_t H, int32_t W, int32_t need_grad0, int32_t need_grad1, int32_t which, size_t* out) {
-    if (!out || H < GS_LPIPS_MIN_SIZE || H > GS_LPIPS_MAX_SIZE || W < GS_LPIPS_MIN_SIZE || W > GS_LPIPS_MAX_SIZE || which < 0 ||
-        which > GS_LPIPS_WS_BACKWARD)
-        return GS_E_BAD_ARG;
-    *out = lpips_workspace_bytes(H, W, need_grad0, need_grad1, which);
-    return GS_OK;
-}
-int gs_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, void* saved, size_t saved_bytes, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-    if (const int rc = lpips_validate(a)) return rc;
-    if (!pose_req(loss) || !pose_a4(per_tap) || !lp_a16(workspace)) return GS_E_BAD_ARG;
-    const size_t need_saved = lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED);
-    if (need_saved && !lp_a16(saved)) return GS_E_BAD_ARG;
-    if (saved_bytes < need_saved ||
-        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_FORWARD))
-        return GS_E_WORKSPACE;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_lpips_forward(a, loss, per_tap, (float*)saved, (float*)workspace, (hipStream_t)stream);
-}
-int gs_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const void* saved,
-                      size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = lpips_validate(a)) return rc;
-    if (!pose_a4(dL_dloss) || !pose_a4(d_in0) || !pose_a4(d_in1)) return GS_E_BAD_ARG;
-    if ((d_in0 && !a->need_grad0) || (d_in1 && !a->need_grad1)) return GS_E_BAD_ARG;
-    if (!d_in0 && !d_in1) return GS_OK;
-    if (!lp_a16(saved) || !lp_a16(workspace)) return GS_E_BAD_ARG;
-    if (saved_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED) ||
-        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_BACKWARD))
-        return GS_E_WORKSPACE;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_lpips_backward(a, dL_dloss, d_in0, d_in1, (const float*)saved, (float*)workspace, (hipStream_t)stream);
-}
-int gs_lpips_conv(const float* packed, int32_t layer, int32_t backward, int32_t normalize, int32_t H, int32_t W, const float* in,
-                  int64_t in_cs, int64_t in_rs, const float* mask, float* out, void* stream) {
-    if (!lp_a16(packed) || layer < 0 || layer >= GS_LPIPS_LAYERS || H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE || W > GS_LPIPS_MAX_SIZE)
-        return GS_E_BAD_ARG;
-    const bool image_in = layer == 0 && !backward, image_out = layer == 0 && backward;
-    if (image_in ? (!pose_req(in) || in_cs < 1 || in_rs < W) : !lp_a16(in)) return GS_E_BAD_ARG;
-    if (image_out ? !pose_req(out) : !lp_a16(out)) return GS_E_BAD_ARG;
-    if (backward && !lp_a16(mask)) return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_lpips_conv(packed, layer, backward, normalize, H, W, in, in_cs, in_rs, mask, out, (hipStream_t)stream);
-}
-int gs_lpips_pool(int32_t backward, int32_t H, int32_t W, int32_t C, const float* in, const float* g, const float* dp, float* out,
-                  void* stream) {
-    if (H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE || W > GS_LPIPS_MAX_SIZE || C < 4 || C > 512 || (C & 3) || !lp_a16(in) || !lp_a16(out))
-        return GS_E_BAD_ARG;
-    if (backward && (!lp_a16(g) || ((H >> 1) && (W >> 1) && !lp_a16(dp)))) return GS_E_BAD_ARG;
-    GS_CAPTURE_OK_IF(stream, true);
-    return launch_lpips_pool(backward, H, W, C, in, g, dp, out, (hipStream_t)stream);
-}
-
-int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
-               void* workspace, size_t workspace_bytes, void* stream) {
-    GS_NO_CAPTURE(stream);
-    if (Nq < 0 || Nr <= 0 || K < 1 || K > 8 || (Nq > 0 && (!queries || !dists || !idx)) || !ref || !workspace) return GS_E_BAD_ARG;
-    if (Nq == 0) return GS_OK;
-    return launch_knn_points(Nq, queries, Nr, ref, K, dists, (long long*)idx, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int gs_pair_stats(const GsFwdArgs* a, const void* geom, size_t geom_bytes, const void* binning, size_t binning_bytes, const void* img,

@@ -642,131 +642,9 @@ int launch_tile_lists(const uint4* ranklist, const uint32_t* chunk_pairs, uint32
                       uint32_t* order, uint32_t* point_list, PairCount pc, LongLists ll, bool totals_zeroed, int debug,
                       hipStream_t s);
 
-// training-step bookkeeping (optim.hip, row N4)
-int launch_densify_stats(int N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
-                         float* xyz_gradient_accum, float* denom, hipStream_t s);
-int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s);
-// the converter's optimizer step (optim.hip): deterministic global gradient norm, in-place scale, extended Adam
-size_t grad_norm_workspace_bytes(int n, const GsGradTensor* tensors);
-int launch_grad_norm(int n, const GsGradTensor* tensors, float max_norm, float* out, float* workspace, hipStream_t s);
-int launch_grad_scale(int n, const GsGradTensor* tensors, const float* clip_coef, hipStream_t s);
-int launch_adam_ex(int n, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
-                   const float* clip_coef, hipStream_t s);
-// densification cycle (densify.hip)
-size_t densify_workspace_bytes(int N);
-int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_host, hipStream_t s);
-int launch_densify_apply(int N, int N_new, const void* workspace, int n, const GsDensifyTensor* tensors,
-                         const float* scaling, const float* rotation, const float* noise, hipStream_t s);
-int launch_reset_opacity(int N, const float* in, float* out, float* exp_avg, float* exp_avg_sq, hipStream_t s);
-// AIAP regularisers (aiap.hip): up to two (xc, xd) sets sharing one neighbour list; the spec is at the top of aiap.hip
-size_t aiap_workspace_bytes(int N, int K);
-int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, void* workspace, hipStream_t s);
-int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
-                         hipStream_t s);
-
-// multiresolution hash-grid encoding (hashgrid.hip; the spec is at its top).  HgTable: the level table, passed to the
-// kernels by value (computed on the host by hashgrid_table, the one source of the integer decisions)
-struct HgTable {
-    int L, F;
-    float scale[GS_HASHGRID_MAX_LEVELS];
-    uint32_t res[GS_HASHGRID_MAX_LEVELS], size[GS_HASHGRID_MAX_LEVELS], off[GS_HASHGRID_MAX_LEVELS + 1];
-};
-int hashgrid_table(const GsHashGrid* g, HgTable* t);
-size_t hashgrid_workspace_bytes(const HgTable& t, int N);
-int launch_hashgrid_forward(const HgTable& t, int N, const float* x, const float* params, float* out, hipStream_t s);
-int launch_hashgrid_backward(const HgTable& t, int N, const float* x, const float* params, const float* dL_dout,
-                             float* dL_dx, float* dL_dparams, void* workspace, hipStream_t s);
-// linear blend skinning of the rigid deformer (skinning.hip; the spec is at its top)
-size_t skinning_workspace_bytes(int N);
-int launch_skin_weights_forward(int N, int kind, const float* logits, float* weights, hipStream_t s);
-int launch_skin_weights_backward(int N, int kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
-                                 hipStream_t s);
-int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
-                            float* xyz_out, float* rot_out, float* T_fwd, hipStream_t s);
-int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
-                             const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
-                             void* workspace, hipStream_t s);
-// the skinning regulariser: mesh surface samples and the fused loss (skinloss.hip; the spec is at its top)
-size_t skin_loss_workspace_bytes(int n);
-int launch_mesh_sample(int n, int V, int F, const float* verts, const int* faces, const float* cdf, const float* vweights,
-                       const float* aabb_min, const float* aabb_inv_extent, const float* draws, float* p_norm, float* target,
-                       int* face, float* bary, float* points, hipStream_t s);
-int launch_skin_loss_forward(int n, int kind, const float* logits, const float* target, float* loss, void* workspace,
-                             hipStream_t s);
-int launch_skin_loss_backward(int n, int kind, const float* logits, const float* target, const float* dL_dloss,
-                              float* dL_dlogits, hipStream_t s);
-// SMPL pose correction (pose.hip; the spec is at its top)
-size_t pose_workspace_bytes(int V);
-int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone, float* loss, float* state, void* workspace,
-                        hipStream_t s);
-int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g_rots, const float* g_Jtrs, const float* g_bone,
-                         const float* g_loss, float* dbetas, float* droot, float* dbody, float* dhand, float* dtrans,
-                         hipStream_t s);
-// the non-rigid deformer around its MLP (nonrigid.hip; the spec is at its top)
-size_t pose_encoder_grad_floats(int d);
-int launch_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, hipStream_t s);
-int launch_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* g_out, float* dparams, float* drots,
-                                 float* dJtrs, hipStream_t s);
-size_t nonrigid_workspace_bytes(int N, int D);
-int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, const float* deltas, const float* xyz, const float* scaling,
-                                  const float* rot, float* xyz_o, float* scal_o, float* rot_o, float* feat, float* losses,
-                                  void* workspace, hipStream_t s);
-int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const float* deltas, const float* scaling, const float* rot,
-                                   const float* g_xyz, const float* g_scal, const float* g_rot, const float* g_feat,
-                                   const float* g_nrx, const float* g_nrs, const float* g_nrr, float* ddeltas, float* dscal,
-                                   float* drot, hipStream_t s);
-// the input of the ColorMLP texture (texture.hip; the spec is at its top).  TxGrads: the block gradients' addresses, by value
-struct TxGrads {
-    float* before[GS_TEXTURE_MAX_BEFORE];
-    float* after[GS_TEXTURE_MAX_AFTER];
-};
-size_t texture_workspace_bytes(int N, int D, int latent_dim);
-int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s);
-int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const TxGrads& grads, float* dxyz, float* dlatent,
-                                  void* workspace, hipStream_t s);
-// the fused VanillaCondMLP (mlp.hip; the spec is at its top)
-size_t mlp_workspace_bytes(const GsMlpArgs* a, int backward);
-int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, hipStream_t s);
-int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, void* workspace, hipStream_t s);
-// the LPIPS-VGG perceptual loss (lpips.hip; the spec is at its top)
-size_t lpips_packed_bytes();
-size_t lpips_workspace_bytes(int H, int W, int grad0, int grad1, int which);
-int lpips_conv_workgroups(int H, int W, int N, int nimg);
-int launch_lpips_pack(const GsLpipsArgs* a, float* packed, hipStream_t s);
-int launch_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, float* saved, float* ws, hipStream_t s);
-int launch_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const float* saved, float* ws,
-                          hipStream_t s);
-int launch_lpips_conv(const float* packed, int layer, int backward, int normalize, int H, int W, const float* in, long long in_cs,
-                      long long in_rs, const float* mask, float* out, hipStream_t s);
-int launch_lpips_pool(int backward, int H, int W, int C, const float* in, const float* g, const float* dp, float* out, hipStream_t s);
-// K nearest reference points of every query (knn.hip, row N4); workspace = knn_ws_bytes(Nr)
-int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
-                      void* ws, size_t ws_bytes, hipStream_t s);
-
-// pre-rasterizer per-Gaussian chains (prepass.hip, row N3)
-int launch_build_cov(int N, const float* scales, float mod, const float* rot, int is_matrix, float* cov6, hipStream_t s);
-int launch_build_cov_bwd(int N, const float* scales, float mod, const float* rot, int is_matrix, const float* dL_dcov6,
-                         float* dL_dscales, float* dL_drot, hipStream_t s);
-int launch_sh2rgb(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
-                  const float* noise_host, float* colors, uint8_t* clamped, hipStream_t s);
-int launch_sh2rgb_bwd(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
-                      const float* noise_host, const uint8_t* clamped, const float* dL_dcolors, float* dL_dshs, float* dL_dxyz,
-                      hipStream_t s);
-
-// fused L1 image loss (loss.hip): loss[0] = mean |x - y|, grad = sign(x - y) / n
-size_t l1_ws_bytes(int64_t n);
-int launch_l1_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s);
-// loss[0] = (partial[0] + ... + partial[nparts - 1], in a fixed order) * inv_n  (the second pass of the L1 / BCE losses; also
-// the fused L1's, whose partials come from the render launch)
+// loss.hip: loss[0] = (partial[0] + ... + partial[nparts - 1], in a fixed order) * inv_n  (the second pass of the L1 / BCE
+// losses; also the fused L1's, whose partials come from the render launch)
 int launch_loss_final(const float* partial, int nparts, float inv_n, float* loss, hipStream_t s);
-int launch_bce_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s);
-// SSIM of two (C,H,W) images + the three partial-derivative maps its backward filters (loss.hip)
-size_t ssim_ws_bytes(int C, int H, int W);
-int launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, float* ssim_out, float* dm_dmu1,
-                        float* dm_ds1, float* dm_ds12, float* partial, hipStream_t s);
-int launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* dm_dmu1,
-                         const float* dm_ds1, const float* dm_ds12, const float* dL_dssim, float* dL_dimg1,
-                         hipStream_t s);
 
 // `fill`: 16-byte words the kernel's other workgroups set to all-ones while the first one orders the tiles (the
 // backward's ROW_UNWRITTEN marks: a fill launch less, and it overlaps the single-workgroup ordering)
@@ -867,5 +745,3 @@ static inline size_t scratch_total_bytes(int64_t D, int P, int ntiles) {
 // report counters (debug_stats.hip): out[0] = pairs composited (alpha >= 1/255 before the pixel is done), out[1] = sum of n_contrib
 int launch_pair_stats(const float* rec, const uint32_t* point_list, const uint32_t* ranges, const uint32_t* n_contrib, int W, int H,
                       unsigned long long* out, hipStream_t s);
-int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes, hipStream_t s);
-size_t knn_ws_bytes(int P);

@@ -35,6 +35,7 @@
 // The count N' stays on the device (and, optionally, is copied to a pinned host word); the apply launch then writes
 // every output tensor by destination index.
 #include "common.h"
+#include "boundary.h"
 
 #define DN_THREADS 256
 #define DN_ITEMS 4                        // sources per thread in classify / map
@@ -77,7 +78,7 @@ static inline size_t dn_carve(int N, char* base, DnWs* w) {
     o += dn_align(2 * (size_t)N * 4);
     return o;
 }
-size_t densify_workspace_bytes(int N) { return dn_carve(N, nullptr, nullptr); }
+static size_t densify_workspace_bytes(int N) { return dn_carve(N, nullptr, nullptr); }
 
 __device__ __forceinline__ float dn_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // torch.max(exp(s), dim=1).values
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(DN_THREADS) void densify_map_kernel(int N, DnWs w) 
     }
 }
 
-int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_host, hipStream_t s) {
+static int launch_densify_plan(const GsDensifyPlan& p, void* workspace, int32_t* count_host, hipStream_t s) {
     DnWs w;
     dn_carve(p.N, (char*)workspace, &w);
     DnPlanArgs a{p.N, p.scaling, p.opacity, p.grad_accum, p.denom, p.prune_mask, p.grad_threshold, p.split_scale,
@@ -311,8 +312,8 @@ __global__ __launch_bounds__(256) void densify_apply_kernel(DnApplyBatch b, cons
     }
 }
 
-int launch_densify_apply(int N, int N_new, const void* workspace, int n, const GsDensifyTensor* tensors,
-                         const float* scaling, const float* rotation, const float* noise, hipStream_t s) {
+static int launch_densify_apply(int N, int N_new, const void* workspace, int n, const GsDensifyTensor* tensors,
+                                const float* scaling, const float* rotation, const float* noise, hipStream_t s) {
     DnWs w;
     dn_carve(N, (char*)const_cast<void*>(workspace), &w);
     DnApplyBatch b;
@@ -344,9 +345,54 @@ __global__ __launch_bounds__(256) void reset_opacity_kernel(int N, const float* 
     if (v) v[i] = 0.0f;
 }
 
-int launch_reset_opacity(int N, const float* in, float* out, float* exp_avg, float* exp_avg_sq, hipStream_t s) {
+static int launch_reset_opacity(int N, const float* in, float* out, float* exp_avg, float* exp_avg_sq, hipStream_t s) {
     StageScope st("reset_opacity", s);
     hipLaunchKernelGGL(reset_opacity_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, in, out, exp_avg, exp_avg_sq);
     GS_LAUNCH_CHECK("reset_opacity", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+// N < 2^30: the map packs a source index and a two-bit slot into 32 bits, and N' <= 2 N stays an int32
+#define GS_DENSIFY_MAX_N (1 << 30)
+int gs_densify_workspace_bytes(int32_t N, size_t* out) {
+    if (!out || N < 0 || N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
+    *out = densify_workspace_bytes(N);
+    return GS_OK;
+}
+int gs_densify_plan(const GsDensifyPlan* p, void* workspace, size_t workspace_bytes, int32_t* count_host_pinned,
+                    void* stream) {
+    GS_CAPTURE_OK_IF(stream, count_host_pinned == nullptr);
+    if (!p || !workspace || p->N < 0 || p->N >= GS_DENSIFY_MAX_N) return GS_E_BAD_ARG;
+    if (p->N > 0 && !p->prune_mask && (!p->scaling || !p->opacity || !p->grad_accum || !p->denom)) return GS_E_BAD_ARG;
+    if (workspace_bytes < densify_workspace_bytes(p->N)) return GS_E_WORKSPACE;
+    return launch_densify_plan(*p, workspace, count_host_pinned, (hipStream_t)stream);
+}
+int gs_densify_apply(int32_t N, int32_t N_new, const void* workspace, size_t workspace_bytes, int32_t n_tensors,
+                     const GsDensifyTensor* tensors, const float* scaling, const float* rotation, const float* noise,
+                     void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || N >= GS_DENSIFY_MAX_N || N_new < 0 || N_new > 2 * N || !workspace || n_tensors < 0 ||
+        n_tensors > GS_DENSIFY_MAX_TENSORS || (n_tensors > 0 && !tensors))
+        return GS_E_BAD_ARG;
+    if (workspace_bytes < densify_workspace_bytes(N)) return GS_E_WORKSPACE;
+    for (int k = 0; k < n_tensors; k++) {
+        const GsDensifyTensor& t = tensors[k];
+        if (t.width <= 0 || t.kind < GS_DENSIFY_COPY || t.kind > GS_DENSIFY_CHILD_SCALING) return GS_E_BAD_ARG;
+        if (N_new > 0 && (!t.dst || (t.kind != GS_DENSIFY_ZERO && !t.src))) return GS_E_BAD_ARG;
+        if ((t.kind == GS_DENSIFY_CHILD_POSITION || t.kind == GS_DENSIFY_CHILD_SCALING) && t.width != 3) return GS_E_BAD_ARG;
+        if (t.kind == GS_DENSIFY_CHILD_POSITION && N_new > 0 && (!scaling || !rotation || !noise)) return GS_E_BAD_ARG;
+    }
+    if (N_new == 0 || n_tensors == 0) return GS_OK;
+    return launch_densify_apply(N, N_new, workspace, n_tensors, tensors, scaling, rotation, noise, (hipStream_t)stream);
+}
+int gs_reset_opacity(int32_t N, const float* opacity_in, float* opacity_out, float* exp_avg, float* exp_avg_sq,
+                     void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (N > 0 && (!opacity_in || !opacity_out))) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_reset_opacity(N, opacity_in, opacity_out, exp_avg, exp_avg_sq, (hipStream_t)stream);
+}
+
+}  // extern "C"

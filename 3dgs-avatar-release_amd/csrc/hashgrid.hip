@@ -49,6 +49,7 @@
 //                   l, l + 64, ..., then the ladder); longer lists add their chunk partials in chunk order, the same way.
 // Every order is fixed: the same input gives the same bits, run after run and under graph replay.
 #include "common.h"
+#include "boundary.h"
 
 #define HG_THREADS 256
 #ifndef HG_HEAVY
@@ -60,8 +61,13 @@
 
 static inline size_t hg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// ---- the level table (host)
-int hashgrid_table(const GsHashGrid* g, HgTable* t) {
+// ---- the level table (host), passed to the kernels by value; hashgrid_table is the one source of the integer decisions
+struct HgTable {
+    int L, F;
+    float scale[GS_HASHGRID_MAX_LEVELS];
+    uint32_t res[GS_HASHGRID_MAX_LEVELS], size[GS_HASHGRID_MAX_LEVELS], off[GS_HASHGRID_MAX_LEVELS + 1];
+};
+static int hashgrid_table(const GsHashGrid* g, HgTable* t) {
     const int L = g->n_levels, F = g->n_features_per_level, T = g->log2_hashmap_size, N0 = g->base_resolution;
     const float b = g->per_level_scale;
     if (L < 1 || L > GS_HASHGRID_MAX_LEVELS || !(F == 1 || F == 2 || F == 4 || F == 8) || T < 1 || T > 30 || N0 < 1 ||
@@ -122,7 +128,7 @@ static inline size_t hg_carve(const HgTable& t, int N, char* base, HgWs* w) {
     }
     return o;
 }
-size_t hashgrid_workspace_bytes(const HgTable& t, int N) { return hg_carve(t, N, nullptr, nullptr); }
+static size_t hashgrid_workspace_bytes(const HgTable& t, int N) { return hg_carve(t, N, nullptr, nullptr); }
 
 // ---- device helpers
 template <int F>
@@ -200,7 +206,7 @@ __device__ __forceinline__ int hg_level_of(const HgTable& t, uint32_t e) {
 template <int F>
 __global__ __launch_bounds__(HG_THREADS) void hg_fwd_kernel(HgTable tab, int N, const float* __restrict__ x,
                                                             const float* __restrict__ theta, float* __restrict__ out) {
-    const uint32_t t = blockIdx.x * HG_THREADS + threadIdx.x;  // (N L < 2^31: capi.hip)
+    const uint32_t t = blockIdx.x * HG_THREADS + threadIdx.x;  // (N L < 2^31: gs_hashgrid_forward)
     if (t >= (uint32_t)N * (uint32_t)tab.L) return;
     const uint32_t i = t / (uint32_t)tab.L;
     const int l = (int)(t - i * (uint32_t)tab.L);
@@ -222,7 +228,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_fwd_kernel(HgTable tab, int N, 
     hg_store<F>(out + (size_t)t * F, acc);
 }
 
-int launch_hashgrid_forward(const HgTable& tab, int N, const float* x, const float* params, float* out, hipStream_t s) {
+static int launch_hashgrid_forward(const HgTable& tab, int N, const float* x, const float* params, float* out, hipStream_t s) {
     const long long n = (long long)N * tab.L;
     const int nb = (int)((n + HG_THREADS - 1) / HG_THREADS);
     StageScope st("hashgrid_fwd", s);
@@ -490,8 +496,8 @@ static int hg_backward(const HgTable& tab, int N, const float* x, const float* p
     return GS_OK;
 }
 
-int launch_hashgrid_backward(const HgTable& tab, int N, const float* x, const float* params, const float* dL_dout,
-                             float* dL_dx, float* dL_dparams, void* workspace, hipStream_t s) {
+static int launch_hashgrid_backward(const HgTable& tab, int N, const float* x, const float* params, const float* dL_dout,
+                                    float* dL_dx, float* dL_dparams, void* workspace, hipStream_t s) {
     switch (tab.F) {
         case 1: return hg_backward<1>(tab, N, x, params, dL_dout, dL_dx, dL_dparams, workspace, s);
         case 2: return hg_backward<2>(tab, N, x, params, dL_dout, dL_dx, dL_dparams, workspace, s);
@@ -499,3 +505,65 @@ int launch_hashgrid_backward(const HgTable& tab, int N, const float* x, const fl
         default: return hg_backward<8>(tab, N, x, params, dL_dout, dL_dx, dL_dparams, workspace, s);
     }
 }
+
+extern "C" {
+
+int gs_hashgrid_levels(const GsHashGrid* grid, int32_t* offsets, float* scales, int32_t* resolutions, int32_t* n_params) {
+    if (!grid) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    for (int l = 0; l <= t.L; l++) {
+        if (offsets) offsets[l] = (int32_t)t.off[l];
+        if (l == t.L) break;
+        if (scales) scales[l] = t.scale[l];
+        if (resolutions) resolutions[l] = (int32_t)t.res[l];
+    }
+    if (n_params) *n_params = (int32_t)(t.off[t.L] * (uint32_t)t.F);
+    return GS_OK;
+}
+// the sort numbers the 8 L N (point, level, corner) pairs with 32-bit words
+static bool hg_pairs_fit(const HgTable& t, int32_t N) { return (int64_t)8 * t.L * N < ((int64_t)1 << 31); }
+int gs_hashgrid_workspace_bytes(const GsHashGrid* grid, int32_t N, size_t* out) {
+    if (!grid || !out || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if (!hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
+    *out = hashgrid_workspace_bytes(t, N);
+    return GS_OK;
+}
+int gs_hashgrid_forward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, float* out, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!grid || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if ((int64_t)N * t.L >= ((int64_t)1 << 31)) return GS_E_TOO_LARGE;
+    if (N == 0 || !out) return GS_OK;
+    const size_t row = (size_t)4 * (t.F < 4 ? t.F : 4);  // a row of F features is read with loads of up to 16 bytes
+    if (!x || !params || !aligned(params, row) || !aligned(out, row) || !aligned(x, 4)) return GS_E_BAD_ARG;
+    return launch_hashgrid_forward(t, N, x, params, out, (hipStream_t)stream);
+}
+int gs_hashgrid_backward(const GsHashGrid* grid, int32_t N, const float* x, const float* params, const float* dL_dout,
+                         float* dL_dx, float* dL_dparams, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!grid || N < 0) return GS_E_BAD_ARG;
+    HgTable t;
+    const int rc = hashgrid_table(grid, &t);
+    if (rc != GS_OK) return rc;
+    if (dL_dparams && !hg_pairs_fit(t, N)) return GS_E_TOO_LARGE;
+    if (!dL_dparams && (N == 0 || !dL_dx)) return GS_OK;
+    if (N > 0 && (!x || !dL_dout || (dL_dx && !params))) return GS_E_BAD_ARG;
+    const size_t row = (size_t)4 * (t.F < 4 ? t.F : 4);
+    if (!aligned(params, row) || !aligned(dL_dout, row) || !aligned(dL_dparams, row) || !aligned(x, 4) || !aligned(dL_dx, 4))
+        return GS_E_BAD_ARG;
+    if (dL_dparams) {
+        if (!workspace) return GS_E_BAD_ARG;
+        if (workspace_bytes < hashgrid_workspace_bytes(t, N)) return GS_E_WORKSPACE;
+    }
+    return launch_hashgrid_backward(t, N, x, params, dL_dout, N > 0 ? dL_dx : nullptr, dL_dparams, workspace,
+                                    (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 // every step of that sequence is monotone, so fl(box distance) <= fl(point distance) for every
 // point inside the box.  Built with -ffp-contract=off so distances match the CPU oracle bit for bit.
 #include "common.h"
+#include "boundary.h"
 #include <float.h>
 
 #define KNN_BOX 64   // points per box of the Morton-ordered reference set (one point per lane of the search's wave)
@@ -37,7 +38,7 @@ static KnnLayout knn_layout(int P) {
     L.total = o;
     return L;
 }
-size_t knn_ws_bytes(int P) { return knn_layout(P).total; }
+static size_t knn_ws_bytes(int P) { return knn_layout(P).total; }
 
 // partial bounding boxes: mm[6 b .. 6 b + 5] = (min xyz, max xyz) of block b's grid-stride share
 // (also clears the radix sort's digit totals on the side: a fill launch less)
@@ -400,8 +401,8 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_scan_kernel(int Nq, const float*
     }
 }
 
-int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
-                      void* ws, size_t ws_bytes, hipStream_t s) {
+static int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
+                             void* ws, size_t ws_bytes, hipStream_t s) {
     const KnnLayout L = knn_layout(Nr);
     if (ws_bytes < L.total) return GS_E_WORKSPACE;
     char* w = (char*)ws;
@@ -447,7 +448,7 @@ int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, in
     return GS_OK;
 }
 
-int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+static int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
     const KnnLayout L = knn_layout(P);
     if (ws_bytes < L.total) return GS_E_WORKSPACE;
     char* w = (char*)ws;
@@ -482,3 +483,27 @@ int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes
     GS_LAUNCH_CHECK("knn.search", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+int knn_workspace_bytes(int32_t P, size_t* out) {
+    if (!out || P < 0) return GS_E_BAD_ARG;
+    *out = knn_ws_bytes(P);
+    return GS_OK;
+}
+int knn_dist2(int32_t P, const float* points, float* mean_d2, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_NO_CAPTURE(stream);  // (the sorts clear their tables with memset nodes: untested under replay)
+    if (P < 0 || (P > 0 && (!points || !mean_d2 || !workspace))) return GS_E_BAD_ARG;
+    if (P == 0) return GS_OK;
+    return launch_knn(P, points, mean_d2, workspace, workspace_bytes, (hipStream_t)stream);
+}
+// workspace = knn_workspace_bytes(Nr)
+int knn_points(int32_t Nq, const float* queries, int32_t Nr, const float* ref, int32_t K, float* dists, int64_t* idx,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    GS_NO_CAPTURE(stream);
+    if (Nq < 0 || Nr <= 0 || K < 1 || K > 8 || (Nq > 0 && (!queries || !dists || !idx)) || !ref || !workspace) return GS_E_BAD_ARG;
+    if (Nq == 0) return GS_OK;
+    return launch_knn_points(Nq, queries, Nr, ref, K, dists, (long long*)idx, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -4,6 +4,7 @@
 // |x - y| per block; a second, single-block pass adds the partials in index order.  No atomics: the
 // result is bitwise reproducible.
 #include "common.h"
+#include "boundary.h"
 #include <math.h>
 
 #define L1_THREADS 256
@@ -80,9 +81,9 @@ static int l1_blocks(int64_t n) {
     return (int)(want < 1 ? 1 : (want > L1_MAX_BLOCKS ? L1_MAX_BLOCKS : want));
 }
 
-size_t l1_ws_bytes(int64_t n) { return (size_t)l1_blocks(n) * sizeof(float); }
+static size_t l1_ws_bytes(int64_t n) { return (size_t)l1_blocks(n) * sizeof(float); }
 
-int launch_bce_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s) {
+static int launch_bce_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s) {
     const int blocks = l1_blocks(n);
     const float inv_n = 1.0f / (float)n;
     StageScope st("bce_loss", s);
@@ -126,7 +127,7 @@ int launch_loss_final(const float* partial, int nparts, float inv_n, float* loss
     return GS_OK;
 }
 
-int launch_l1_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s) {
+static int launch_l1_loss(const float* x, const float* y, int64_t n, float* loss, float* grad, float* partial, hipStream_t s) {
     const int blocks = l1_blocks(n);
     const float inv_n = 1.0f / (float)n;
     StageScope st("l1_loss", s);
@@ -393,10 +394,10 @@ static SsimWindow ssim_window() {
 }
 
 static inline int ssim_tiles(int v) { return (v + SS_T - 1) / SS_T; }
-size_t ssim_ws_bytes(int C, int H, int W) { return (size_t)C * ssim_tiles(H) * ssim_tiles(W) * sizeof(float); }
+static size_t ssim_ws_bytes(int C, int H, int W) { return (size_t)C * ssim_tiles(H) * ssim_tiles(W) * sizeof(float); }
 
-int launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, float* ssim_out, float* dm_dmu1,
-                        float* dm_ds1, float* dm_ds12, float* partial, hipStream_t s) {
+static int launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, float* ssim_out, float* dm_dmu1,
+                               float* dm_ds1, float* dm_ds12, float* partial, hipStream_t s) {
     const dim3 grid(ssim_tiles(W), ssim_tiles(H), C);
     StageScope st("ssim_fwd", s);
     hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(SS_NT), 0, s, H, W, img1, img2, ssim_window(), dm_dmu1, dm_ds1,
@@ -408,9 +409,9 @@ int launch_ssim_forward(int C, int H, int W, const float* img1, const float* img
     return GS_OK;
 }
 
-int launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* dm_dmu1,
-                         const float* dm_ds1, const float* dm_ds12, const float* dL_dssim, float* dL_dimg1,
-                         hipStream_t s) {
+static int launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* dm_dmu1,
+                                const float* dm_ds1, const float* dm_ds12, const float* dL_dssim, float* dL_dimg1,
+                                hipStream_t s) {
     const dim3 grid(ssim_tiles(W), ssim_tiles(H), C);
     StageScope st("ssim_bwd", s);
     hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(SS_NT), 0, s, H, W, img1, img2, ssim_window(), dm_dmu1, dm_ds1,
@@ -418,3 +419,53 @@ int launch_ssim_backward(int C, int H, int W, const float* img1, const float* im
     GS_LAUNCH_CHECK("ssim.backward", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+int gs_l1_loss_workspace_bytes(int64_t n, size_t* out) {
+    if (!out || n < 0) return GS_E_BAD_ARG;
+    *out = l1_ws_bytes(n);
+    return GS_OK;
+}
+int gs_l1_loss(int64_t n, const float* x, const float* y, float* loss, float* dL_dx, void* workspace, size_t workspace_bytes,
+               void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n <= 0 || !x || !y || !loss || !dL_dx || !workspace) return GS_E_BAD_ARG;
+    if (!aligned(x, 16) || !aligned(y, 16) || !aligned(dL_dx, 16)) return GS_E_BAD_ARG;  // float4 accesses
+    if (workspace_bytes < l1_ws_bytes(n)) return GS_E_WORKSPACE;
+    return launch_l1_loss(x, y, n, loss, dL_dx, (float*)workspace, (hipStream_t)stream);
+}
+
+int gs_bce_loss(int64_t n, const float* x, const float* y, float* loss, float* dL_dx, void* workspace, size_t workspace_bytes,
+                void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n <= 0 || !x || !y || !loss || !dL_dx || !workspace) return GS_E_BAD_ARG;
+    if (workspace_bytes < l1_ws_bytes(n)) return GS_E_WORKSPACE;
+    return launch_bce_loss(x, y, n, loss, dL_dx, (float*)workspace, (hipStream_t)stream);
+}
+
+int gs_ssim_workspace_bytes(int32_t C, int32_t H, int32_t W, size_t* out) {
+    if (!out || C <= 0 || H <= 0 || W <= 0) return GS_E_BAD_ARG;
+    *out = ssim_ws_bytes(C, H, W);
+    return GS_OK;
+}
+int gs_ssim_forward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_out, float* dm_dmu1,
+                    float* dm_dsigma1_sq, float* dm_dsigma12, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !ssim_out || !workspace) return GS_E_BAD_ARG;
+    if ((dm_dmu1 != nullptr) != (dm_dsigma1_sq != nullptr) || (dm_dmu1 != nullptr) != (dm_dsigma12 != nullptr)) return GS_E_BAD_ARG;
+    if (workspace_bytes < ssim_ws_bytes(C, H, W)) return GS_E_WORKSPACE;
+    return launch_ssim_forward(C, H, W, img1, img2, ssim_out, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, (float*)workspace,
+                               (hipStream_t)stream);
+}
+int gs_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, const float* dm_dmu1,
+                     const float* dm_dsigma1_sq, const float* dm_dsigma12, const float* dL_dssim, float* dL_dimg1,
+                     void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dssim || !dL_dimg1)
+        return GS_E_BAD_ARG;
+    return launch_ssim_backward(C, H, W, img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dssim, dL_dimg1,
+                                (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -48,6 +48,7 @@
 //                    pixel sums of both kernels are compensated (Kahan): fp32 operations in a fixed order.
 //   lp_pack_kernel   the weights for both directions, once, when they are loaded.
 #include "common.h"
+#include "boundary.h"
 
 #define LP_THREADS 256
 #define LP_TS 8     // tile edge: 64 pixels, 16 per wave
@@ -83,7 +84,7 @@ static inline LpOff lp_offsets() {
     o.total = at;
     return o;
 }
-size_t lpips_packed_bytes() { return lp_offsets().total * sizeof(float); }
+static size_t lpips_packed_bytes() { return lp_offsets().total * sizeof(float); }
 static inline size_t lp_head_blocks(int H, int W, int k) { return (lp_npix(H, W, k) + LP_HEAD_PIX - 1) / LP_HEAD_PIX; }
 // floats an image that needs a gradient saves: thirteen post-activations, then five head gradients
 static inline size_t lp_saved_floats(int H, int W) {
@@ -93,7 +94,7 @@ static inline size_t lp_saved_floats(int H, int W) {
     return n;
 }
 // which: 0 the forward's transient workspace, 1 what the forward saves, 2 the backward's transient workspace
-size_t lpips_workspace_bytes(int H, int W, int grad0, int grad1, int which) {
+static size_t lpips_workspace_bytes(int H, int W, int grad0, int grad1, int which) {
     const size_t full = (size_t)64 * lp_npix(H, W, 0), half = (size_t)64 * lp_npix(H, W, 1);
     const int ng = (grad0 ? 1 : 0) + (grad1 ? 1 : 0);
     size_t n = 0;
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(LP_THREADS) void lp_pack_kernel(GsLpipsArgs a, floa
 }
 
 // ---- launchers (the C ABI has checked every argument)
-int launch_lpips_pack(const GsLpipsArgs* a, float* packed, hipStream_t s) {
+static int launch_lpips_pack(const GsLpipsArgs* a, float* packed, hipStream_t s) {
     StageScope st("lpips_pack", s);
     hipLaunchKernelGGL(lp_pack_kernel, dim3(256, LP_LAYERS + 1), dim3(LP_THREADS), 0, s, *a, packed, lp_offsets());
     GS_LAUNCH_CHECK("lpips_pack", 0, s);
@@ -438,7 +439,7 @@ static inline void lp_conv_grid(int H, int W, int N, int nimg, int* nt, int* gx,
     *gx = tiles;
     *gy = (n16 + pick - 1) / pick;
 }
-int lpips_conv_workgroups(int H, int W, int N, int nimg) {
+static int lpips_conv_workgroups(int H, int W, int N, int nimg) {
     int nt, gx, gy;
     lp_conv_grid(H, W, N, nimg, &nt, &gx, &gy);
     return gx * gy;
@@ -472,8 +473,8 @@ static LpConv lp_layer(const float* packed, int l, int backward, int H, int W) {
     c.out_sc = 1; c.out_sx = c.N; c.out_sy = (long long)W * c.N;
     return c;
 }
-int launch_lpips_conv(const float* packed, int layer, int backward, int normalize, int H, int W, const float* in, long long in_cs,
-                      long long in_rs, const float* mask, float* out, hipStream_t s) {
+static int launch_lpips_conv(const float* packed, int layer, int backward, int normalize, int H, int W, const float* in, long long in_cs,
+                             long long in_rs, const float* mask, float* out, hipStream_t s) {
     StageScope st("lpips_conv", s);
     LpConv c = lp_layer(packed, layer, backward, H, W);
     c.in[0] = in; c.mask[0] = backward ? mask : nullptr; c.out[0] = out;
@@ -488,7 +489,7 @@ int launch_lpips_conv(const float* packed, int layer, int backward, int normaliz
     return lp_launch_conv(c, 1, s);
 }
 
-int launch_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, float* saved, float* ws, hipStream_t s) {
+static int launch_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, float* saved, float* ws, hipStream_t s) {
     StageScope st("lpips", s);
     const int H = a->H, W = a->W;
     const LpOff o = lp_offsets();
@@ -578,8 +579,8 @@ int launch_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, floa
     return GS_OK;
 }
 
-int launch_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const float* saved, float* ws,
-                          hipStream_t s) {
+static int launch_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const float* saved, float* ws,
+                                 hipStream_t s) {
     StageScope st("lpips_bwd", s);
     const int H = a->H, W = a->W;
     const size_t full = (size_t)64 * lp_npix(H, W, 0), per_saved = lp_saved_floats(H, W);
@@ -638,7 +639,7 @@ int launch_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_
     return GS_OK;
 }
 // the pools on caller-given maps (tests): backward = 0: out (H / 2, W / 2, C) = pool(in); 1: out (H, W, C) = g + unpool(dp)
-int launch_lpips_pool(int backward, int H, int W, int C, const float* in, const float* g, const float* dp, float* out, hipStream_t s) {
+static int launch_lpips_pool(int backward, int H, int W, int C, const float* in, const float* g, const float* dp, float* out, hipStream_t s) {
     LpPool p = {};
     p.H = H; p.W = W; p.C = C;
     p.in[0] = in; p.g[0] = g; p.dp[0] = dp; p.out[0] = out;
@@ -651,3 +652,83 @@ int launch_lpips_pool(int backward, int H, int W, int C, const float* in, const 
     GS_LAUNCH_CHECK("lpips_pool", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+static int lpips_validate(const GsLpipsArgs* a) {
+    if (!a || a->H < GS_LPIPS_MIN_SIZE || a->H > GS_LPIPS_MAX_SIZE || a->W < GS_LPIPS_MIN_SIZE || a->W > GS_LPIPS_MAX_SIZE)
+        return GS_E_BAD_ARG;
+    if (!required(a->in0, 4) || !required(a->in1, 4) || !required(a->packed, 16)) return GS_E_BAD_ARG;
+    if (a->cs0 < 1 || a->cs1 < 1 || a->rs0 < a->W || a->rs1 < a->W) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_lpips_packed_bytes(size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    *out = lpips_packed_bytes();
+    return GS_OK;
+}
+int gs_lpips_pack_weights(const GsLpipsArgs* a, void* packed, size_t packed_bytes, void* stream) {
+    if (!a || !required(packed, 16) || !aligned(a->shift, 4) || !aligned(a->scale, 4)) return GS_E_BAD_ARG;
+    for (int l = 0; l < GS_LPIPS_LAYERS; l++)
+        if (!required(a->weight[l], 4) || !required(a->bias[l], 4)) return GS_E_BAD_ARG;
+    for (int k = 0; k < GS_LPIPS_TAPS; k++)
+        if (!required(a->lin[k], 4)) return GS_E_BAD_ARG;
+    if (packed_bytes < lpips_packed_bytes()) return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_pack(a, (float*)packed, (hipStream_t)stream);
+}
+int gs_lpips_workspace_bytes(int32_t H, int32_t W, int32_t need_grad0, int32_t need_grad1, int32_t which, size_t* out) {
+    if (!out || H < GS_LPIPS_MIN_SIZE || H > GS_LPIPS_MAX_SIZE || W < GS_LPIPS_MIN_SIZE || W > GS_LPIPS_MAX_SIZE || which < 0 ||
+        which > GS_LPIPS_WS_BACKWARD)
+        return GS_E_BAD_ARG;
+    *out = lpips_workspace_bytes(H, W, need_grad0, need_grad1, which);
+    return GS_OK;
+}
+int gs_lpips_forward(const GsLpipsArgs* a, float* loss, float* per_tap, void* saved, size_t saved_bytes, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (const int rc = lpips_validate(a)) return rc;
+    if (!required(loss, 4) || !aligned(per_tap, 4) || !required(workspace, 16)) return GS_E_BAD_ARG;
+    const size_t need_saved = lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED);
+    if (need_saved && !required(saved, 16)) return GS_E_BAD_ARG;
+    if (saved_bytes < need_saved ||
+        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_FORWARD))
+        return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_forward(a, loss, per_tap, (float*)saved, (float*)workspace, (hipStream_t)stream);
+}
+int gs_lpips_backward(const GsLpipsArgs* a, const float* dL_dloss, float* d_in0, float* d_in1, const void* saved,
+                      size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = lpips_validate(a)) return rc;
+    if (!aligned(dL_dloss, 4) || !aligned(d_in0, 4) || !aligned(d_in1, 4)) return GS_E_BAD_ARG;
+    if ((d_in0 && !a->need_grad0) || (d_in1 && !a->need_grad1)) return GS_E_BAD_ARG;
+    if (!d_in0 && !d_in1) return GS_OK;
+    if (!required(saved, 16) || !required(workspace, 16)) return GS_E_BAD_ARG;
+    if (saved_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_SAVED) ||
+        workspace_bytes < lpips_workspace_bytes(a->H, a->W, a->need_grad0, a->need_grad1, GS_LPIPS_WS_BACKWARD))
+        return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_backward(a, dL_dloss, d_in0, d_in1, (const float*)saved, (float*)workspace, (hipStream_t)stream);
+}
+int gs_lpips_conv(const float* packed, int32_t layer, int32_t backward, int32_t normalize, int32_t H, int32_t W, const float* in,
+                  int64_t in_cs, int64_t in_rs, const float* mask, float* out, void* stream) {
+    if (!required(packed, 16) || layer < 0 || layer >= GS_LPIPS_LAYERS || H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE ||
+        W > GS_LPIPS_MAX_SIZE)
+        return GS_E_BAD_ARG;
+    const bool image_in = layer == 0 && !backward, image_out = layer == 0 && backward;
+    if (image_in ? (!required(in, 4) || in_cs < 1 || in_rs < W) : !required(in, 16)) return GS_E_BAD_ARG;
+    if (image_out ? !required(out, 4) : !required(out, 16)) return GS_E_BAD_ARG;
+    if (backward && !required(mask, 16)) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_conv(packed, layer, backward, normalize, H, W, in, in_cs, in_rs, mask, out, (hipStream_t)stream);
+}
+int gs_lpips_pool(int32_t backward, int32_t H, int32_t W, int32_t C, const float* in, const float* g, const float* dp, float* out,
+                  void* stream) {
+    if (H < 1 || W < 1 || H > GS_LPIPS_MAX_SIZE || W > GS_LPIPS_MAX_SIZE || C < 4 || C > 512 || (C & 3) || !required(in, 16) ||
+        !required(out, 16))
+        return GS_E_BAD_ARG;
+    if (backward && (!required(g, 16) || ((H >> 1) && (W >> 1) && !required(dp, 16)))) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_lpips_pool(backward, H, W, C, in, g, dp, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -44,6 +44,7 @@
 // calls are capture-safe.  LDS strides are chosen so that the MFMA operand reads (16 lanes along one index, 4 along the
 // other) touch 64 distinct banks: 4 x odd where the 16 lanes walk rows, 16 mod 32 where they walk columns.
 #include "common.h"
+#include "boundary.h"
 
 #define ML_THREADS 512
 #define ML_WAVES 8
@@ -91,7 +92,7 @@ static inline int ml_lowest(const GsMlpArgs& a) {
         if (ml_wanted(a, l)) return l;
     return a.n_hidden + 1;
 }
-size_t mlp_workspace_bytes(const GsMlpArgs* a, int backward) {
+static size_t mlp_workspace_bytes(const GsMlpArgs* a, int backward) {
     if (a->N == 0) return 0;
     if (!backward) return a->dim_cond > 0 ? (size_t)a->width * sizeof(float) : 0;
     // dz_0 .. dz_{n_hidden-1}, then the partials
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(ML_FINAL_THREADS) void ml_final_kernel(GsMlpArgs a,
 }
 
 // ---- launchers (the C ABI has checked every argument)
-int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, hipStream_t s) {
+static int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, hipStream_t s) {
     StageScope st("mlp", s);
     float* b0 = nullptr;
     if (a->dim_cond > 0) {
@@ -437,7 +438,7 @@ int launch_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspac
     GS_LAUNCH_CHECK("mlp", 0, s);
     return GS_OK;
 }
-int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, void* workspace, hipStream_t s) {
+static int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, void* workspace, hipStream_t s) {
     StageScope st("mlp_bwd", s);
     const int nl = a->n_hidden + 1, lowest = ml_lowest(*a);
     if (lowest > a->n_hidden) return GS_OK;
@@ -461,3 +462,59 @@ int launch_mlp_backward(const GsMlpArgs* a, const float* acts, const float* g, v
     GS_LAUNCH_CHECK("mlp_final", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+static int mlp_validate(const GsMlpArgs* a) {
+    if (!a || a->N < 0 || a->width < 32 || a->width > GS_MLP_MAX_WIDTH || a->width % 32 != 0 || a->n_hidden < 1 ||
+        a->n_hidden > GS_MLP_MAX_HIDDEN || a->dim_in < 1 || a->dim_in > GS_MLP_MAX_IN || a->dim_cond < 0 ||
+        a->dim_cond > GS_MLP_MAX_COND || a->dim_out < 1 || a->dim_out > GS_MLP_MAX_OUT || !(a->slope == a->slope))
+        return GS_E_BAD_ARG;
+    return GS_OK;
+}
+// x, the condition and every layer's parameters
+static bool mlp_inputs_ok(const GsMlpArgs* a) {
+    if (!required(a->x, 16) || (a->dim_cond > 0 && !required(a->cond, 4))) return false;
+    for (int l = 0; l <= a->n_hidden; l++)
+        if (!required(a->W[l], 4) || !required(a->b[l], 4)) return false;
+    return true;
+}
+int gs_mlp_workspace_bytes(const GsMlpArgs* a, int32_t backward, size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    if (const int rc = mlp_validate(a)) return rc;
+    *out = mlp_workspace_bytes(a, backward != 0);
+    return GS_OK;
+}
+int gs_mlp_forward(const GsMlpArgs* a, float* y, float* acts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mlp_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!mlp_inputs_ok(a) || !required(y, 4) || !aligned(acts, 16)) return GS_E_BAD_ARG;
+    if (a->dim_cond > 0) {
+        if (!required(workspace, 4)) return GS_E_BAD_ARG;
+        if (workspace_bytes < mlp_workspace_bytes(a, 0)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_mlp_forward(a, y, acts, workspace, (hipStream_t)stream);
+}
+int gs_mlp_backward(const GsMlpArgs* a, const float* acts, const float* dL_dy, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    if (const int rc = mlp_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!mlp_inputs_ok(a) || !required(acts, 16) || !required(dL_dy, 16) || !aligned(a->dx, 4) || !aligned(a->dcond, 4))
+        return GS_E_BAD_ARG;
+    if (a->dcond && a->dim_cond == 0) return GS_E_BAD_ARG;
+    bool any = a->dx || a->dcond;
+    for (int l = 0; l <= a->n_hidden; l++) {
+        if (!aligned(a->dW[l], 4) || !aligned(a->db[l], 4)) return GS_E_BAD_ARG;
+        any = any || a->dW[l] || a->db[l];
+    }
+    if (any) {
+        if (!required(workspace, 16)) return GS_E_BAD_ARG;
+        if (workspace_bytes < mlp_workspace_bytes(a, 1)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!any) return GS_OK;
+    return launch_mlp_backward(a, acts, dL_dy, workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

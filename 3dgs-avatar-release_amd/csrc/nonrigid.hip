@@ -59,6 +59,7 @@
 // No atomics, no memsets, no host synchronisation: every output and gradient is bitwise reproducible and the calls are
 // capture-safe.
 #include "common.h"
+#include "boundary.h"
 
 // ---------------------------------------------------------------------------------------------
 // 1. the pose encoder
@@ -75,7 +76,7 @@ static_assert(2 * ENC_J * ENC_MAXM == GS_POSE_ENC_STATE_FLOATS, "state layout");
 static_assert(ENC_J * ENC_MAXM <= ENC_THREADS && ENC_MAXD * ENC_L0_LANES <= ENC_THREADS, "one thread per row");
 static_assert(ENC_L0_LANES * 9 == ENC_X, "layer 0 split");
 
-size_t pose_encoder_grad_floats(int d) {
+static size_t pose_encoder_grad_floats(int d) {
     const size_t m = 13 + (size_t)d;
     return (size_t)ENC_X * d + d + ENC_J * (m * m + m + d * m + d);
 }
@@ -285,14 +286,14 @@ __global__ __launch_bounds__(ENC_THREADS) void pose_enc_bwd_kernel(GsPoseEncArgs
     }
 }
 
-int launch_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, hipStream_t s) {
+static int launch_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, hipStream_t s) {
     StageScope st("pose_encoder", s);
     hipLaunchKernelGGL(pose_enc_fwd_kernel, dim3(1), dim3(ENC_THREADS), 0, s, *a, out, state);
     GS_LAUNCH_CHECK("pose_encoder", 0, s);
     return GS_OK;
 }
-int launch_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* g_out, float* dparams, float* drots,
-                                 float* dJtrs, hipStream_t s) {
+static int launch_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* g_out, float* dparams, float* drots,
+                                        float* dJtrs, hipStream_t s) {
     StageScope st("pose_encoder_bwd", s);
     hipLaunchKernelGGL(pose_enc_bwd_kernel, dim3(1), dim3(ENC_THREADS), 0, s, *a, state, g_out, dparams, drots, dJtrs);
     GS_LAUNCH_CHECK("pose_encoder_bwd", 0, s);
@@ -315,7 +316,7 @@ static inline int nr_blocks(int N, int D) {
     const int R = nr_rows(D);
     return (N + R - 1) / R;
 }
-size_t nonrigid_workspace_bytes(int N, int D) { return (size_t)3 * nr_blocks(N, D) * sizeof(float); }
+static size_t nonrigid_workspace_bytes(int N, int D) { return (size_t)3 * nr_blocks(N, D) * sizeof(float); }
 
 __device__ __forceinline__ float nr_sign(float x) { return x > 0.0f ? 1.0f : x < 0.0f ? -1.0f : 0.0f; }
 
@@ -526,9 +527,9 @@ __global__ __launch_bounds__(NR_THREADS) void nr_apply_bwd_kernel(int N, int D, 
 }
 
 // ---- launchers (the C ABI has checked every argument)
-int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, const float* deltas, const float* xyz, const float* scaling,
-                                  const float* rot, float* xyz_o, float* scal_o, float* rot_o, float* feat, float* losses,
-                                  void* workspace, hipStream_t s) {
+static int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, const float* deltas, const float* xyz, const float* scaling,
+                                         const float* rot, float* xyz_o, float* scal_o, float* rot_o, float* feat, float* losses,
+                                         void* workspace, hipStream_t s) {
     StageScope st("nonrigid_apply", s);
     const int nb = nr_blocks(N, D);
     float* partial = losses ? reinterpret_cast<float*>(workspace) : nullptr;
@@ -541,10 +542,10 @@ int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, const floa
     }
     return GS_OK;
 }
-int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const float* deltas, const float* scaling, const float* rot,
-                                   const float* g_xyz, const float* g_scal, const float* g_rot, const float* g_feat,
-                                   const float* g_nrx, const float* g_nrs, const float* g_nrr, float* ddeltas, float* dscal,
-                                   float* drot, hipStream_t s) {
+static int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const float* deltas, const float* scaling, const float* rot,
+                                          const float* g_xyz, const float* g_scal, const float* g_rot, const float* g_feat,
+                                          const float* g_nrx, const float* g_nrs, const float* g_nrr, float* ddeltas, float* dscal,
+                                          float* drot, hipStream_t s) {
     StageScope st("nonrigid_apply_bwd", s);
     hipLaunchKernelGGL(nr_apply_bwd_kernel, dim3(nr_blocks(N, D)), dim3(NR_THREADS), 0, s, N, D, nr_rows(D), smode, rmode,
                        1.0f / (float)N, deltas, scaling, rot, g_xyz, g_scal, g_rot, g_feat, g_nrx, g_nrs, g_nrr, ddeltas, dscal,
@@ -552,3 +553,89 @@ int launch_nonrigid_apply_backward(int N, int D, int smode, int rmode, const flo
     GS_LAUNCH_CHECK("nonrigid_apply_bwd", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+static int pose_enc_validate(const GsPoseEncArgs* a) {
+    if (!a || a->d < 1 || a->d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
+    for (int i = 1; i < GS_POSE_ENC_JOINTS; i++)
+        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
+    if (!required(a->W0, 4)) return GS_E_BAD_ARG;
+    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
+        if (!required(a->W1[j], 4) || !required(a->W2[j], 4)) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_pose_encoder_grad_floats(int32_t d, size_t* out) {
+    if (!out || d < 1 || d > GS_POSE_ENC_MAX_DIM) return GS_E_BAD_ARG;
+    *out = pose_encoder_grad_floats(d);
+    return GS_OK;
+}
+int gs_pose_encoder_forward(const GsPoseEncArgs* a, float* out, float* state, void* stream) {
+    if (const int rc = pose_enc_validate(a)) return rc;
+    if (!required(a->rots, 4) || !required(a->Jtrs, 4) || !required(a->b0, 4) || !required(out, 4) || !required(state, 4))
+        return GS_E_BAD_ARG;
+    for (int j = 0; j < GS_POSE_ENC_JOINTS; j++)
+        if (!required(a->b1[j], 4) || !required(a->b2[j], 4)) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_pose_encoder_forward(a, out, state, (hipStream_t)stream);
+}
+int gs_pose_encoder_backward(const GsPoseEncArgs* a, const float* state, const float* dL_dout, float* dL_dparams,
+                             float* dL_drots, float* dL_dJtrs, void* stream) {
+    if (const int rc = pose_enc_validate(a)) return rc;
+    if (!required(state, 4) || !required(dL_dout, 4) || !aligned(dL_dparams, 4) || !aligned(dL_drots, 4) || !aligned(dL_dJtrs, 4))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_dparams && !dL_drots && !dL_dJtrs) return GS_OK;
+    return launch_pose_encoder_backward(a, state, dL_dout, dL_dparams, dL_drots, dL_dJtrs, (hipStream_t)stream);
+}
+static bool nr_shape_ok(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset) {
+    return N >= 0 && D >= 10 && D <= GS_NONRIGID_MAX_D &&
+           (scale_offset == GS_NR_SCALE_LOGIT || scale_offset == GS_NR_SCALE_EXP || scale_offset == GS_NR_SCALE_ZERO) &&
+           (rot_offset == GS_NR_ROT_ADD || rot_offset == GS_NR_ROT_MULT);
+}
+int gs_nonrigid_workspace_bytes(int32_t N, int32_t D, size_t* out) {
+    if (!out || N < 0 || D < 10 || D > GS_NONRIGID_MAX_D) return GS_E_BAD_ARG;
+    *out = nonrigid_workspace_bytes(N, D);
+    return GS_OK;
+}
+int gs_nonrigid_apply_forward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                              const float* xyz, const float* scaling, const float* rotation, float* xyz_out,
+                              float* scaling_out, float* rotation_out, float* feature, float* losses, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!deltas || !xyz || !rotation || !xyz_out || !rotation_out || (D > 10 && !feature)) return GS_E_BAD_ARG;
+    if (scale_offset != GS_NR_SCALE_ZERO && (!scaling || !scaling_out)) return GS_E_BAD_ARG;
+    if (scaling_out && !scaling) return GS_E_BAD_ARG;
+    if (!aligned(deltas, 16) || !aligned(rotation, 16) || !aligned(rotation_out, 16) || !aligned(feature, 16) || !aligned(xyz, 4) ||
+        !aligned(scaling, 4) || !aligned(xyz_out, 4) || !aligned(scaling_out, 4) || !aligned(losses, 4))
+        return GS_E_BAD_ARG;
+    if (losses) {
+        if (!required(workspace, 4)) return GS_E_BAD_ARG;
+        if (workspace_bytes < nonrigid_workspace_bytes(N, D)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_nonrigid_apply_forward(N, D, scale_offset, rot_offset, deltas, xyz, scaling, rotation, xyz_out, scaling_out,
+                                         rotation_out, D > 10 ? feature : nullptr, losses, workspace, (hipStream_t)stream);
+}
+int gs_nonrigid_apply_backward(int32_t N, int32_t D, int32_t scale_offset, int32_t rot_offset, const float* deltas,
+                               const float* scaling, const float* rotation, const float* dL_dxyz_out,
+                               const float* dL_dscaling_out, const float* dL_drotation_out, const float* dL_dfeature,
+                               const float* dL_dnr_xyz, const float* dL_dnr_scale, const float* dL_dnr_rot,
+                               float* dL_ddeltas, float* dL_dscaling, float* dL_drotation, void* stream) {
+    if (!nr_shape_ok(N, D, scale_offset, rot_offset)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!deltas || (scale_offset == GS_NR_SCALE_EXP && !scaling) || (rot_offset == GS_NR_ROT_MULT && !rotation)) return GS_E_BAD_ARG;
+    if (!aligned(deltas, 16) || !aligned(rotation, 16) || !aligned(dL_drotation_out, 16) || !aligned(dL_dfeature, 16) ||
+        !aligned(dL_ddeltas, 16) || !aligned(dL_drotation, 16) || !aligned(scaling, 4) || !aligned(dL_dxyz_out, 4) ||
+        !aligned(dL_dscaling_out, 4) || !aligned(dL_dnr_xyz, 4) || !aligned(dL_dnr_scale, 4) || !aligned(dL_dnr_rot, 4) ||
+        !aligned(dL_dscaling, 4))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_ddeltas && !dL_dscaling && !dL_drotation) return GS_OK;
+    return launch_nonrigid_apply_backward(N, D, scale_offset, rot_offset, deltas, scaling, rotation, dL_dxyz_out, dL_dscaling_out,
+                                          dL_drotation_out, D > 10 ? dL_dfeature : nullptr, dL_dnr_xyz, dL_dnr_scale, dL_dnr_rot,
+                                          dL_ddeltas, dL_dscaling, dL_drotation, (hipStream_t)stream);
+}
+
+}  // extern "C"

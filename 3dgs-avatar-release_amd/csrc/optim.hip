@@ -6,6 +6,7 @@
 //     (lr per group, eps 1e-15): the foreach implementation launches ~10 kernels per group.
 // Here: one streaming kernel for the statistics and ONE launch for the Adam step of all tensors.
 #include "common.h"
+#include "boundary.h"
 
 __global__ __launch_bounds__(256) void densify_stats_kernel(int N, const int32_t* __restrict__ radii,
                                                             const float* __restrict__ viewspace_grad,
@@ -22,8 +23,8 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int N, const int32_t
     denom[i] += 1.0f;
 }
 
-int launch_densify_stats(int N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
-                         float* xyz_gradient_accum, float* denom, hipStream_t s) {
+static int launch_densify_stats(int N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
+                                float* xyz_gradient_accum, float* denom, hipStream_t s) {
     StageScope st("densify_stats", s);
     hipLaunchKernelGGL(densify_stats_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, radii, viewspace_grad, max_radii2D,
                        xyz_gradient_accum, denom);
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamBatch b, float w1, float 
     }
 }
 
-int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s) {
+static int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s) {
     AdamBatch b;
     b.n = n;
     long long chunks = 0;
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(AdamExBatch b, double beta
 
 static inline long long opt_chunks(long long n) { return (n + OPT_CHUNK - 1) / OPT_CHUNK; }
 
-size_t grad_norm_workspace_bytes(int n, const GsGradTensor* tensors) {
+static size_t grad_norm_workspace_bytes(int n, const GsGradTensor* tensors) {
     long long chunks = 0;
     for (int k = 0; k < n; k++) chunks += opt_chunks(tensors[k].n);
     return (size_t)(chunks > 0 ? chunks : 1) * sizeof(float);
@@ -303,7 +304,7 @@ static int next_grad_batch(int n, const GsGradTensor* tensors, int k, GradBatch&
     return k;
 }
 
-int launch_grad_norm(int n, const GsGradTensor* tensors, float max_norm, float* out, float* workspace, hipStream_t s) {
+static int launch_grad_norm(int n, const GsGradTensor* tensors, float max_norm, float* out, float* workspace, hipStream_t s) {
     StageScope st("grad_norm", s);
     GradBatch b;
     long long done = 0;
@@ -319,7 +320,7 @@ int launch_grad_norm(int n, const GsGradTensor* tensors, float max_norm, float* 
     return GS_OK;
 }
 
-int launch_grad_scale(int n, const GsGradTensor* tensors, const float* clip_coef, hipStream_t s) {
+static int launch_grad_scale(int n, const GsGradTensor* tensors, const float* clip_coef, hipStream_t s) {
     StageScope st("grad_scale", s);
     GradBatch b;
     for (int k = 0; k < n;) {
@@ -331,8 +332,8 @@ int launch_grad_scale(int n, const GsGradTensor* tensors, const float* clip_coef
     return GS_OK;
 }
 
-int launch_adam_ex(int n, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
-                   const float* clip_coef, hipStream_t s) {
+static int launch_adam_ex(int n, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
+                          const float* clip_coef, hipStream_t s) {
     StageScope st("adam_ex", s);
     // every device step number first, each in a launch of its own in front of the updates
     {
@@ -372,3 +373,76 @@ int launch_adam_ex(int n, const GsAdamTensorEx* tensors, double beta1, double be
     }
     return GS_OK;
 }
+
+extern "C" {
+
+int gs_densify_stats(int32_t N, const int32_t* radii, const float* viewspace_grad, float* max_radii2D,
+                     float* xyz_gradient_accum, float* denom, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (N > 0 && (!radii || !viewspace_grad || !max_radii2D || !xyz_gradient_accum || !denom))) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_densify_stats(N, radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, (hipStream_t)stream);
+}
+int gs_adam_step(int32_t n_tensors, const GsAdamTensor* tensors, double beta1, double beta2, double eps, int64_t step,
+                 void* stream) {
+    GS_NO_CAPTURE(stream);  // (the step number is a host scalar: a replay would repeat the captured step's bias correction)
+    if (n_tensors < 0 || n_tensors > GS_ADAM_MAX_TENSORS || (n_tensors > 0 && !tensors) || step < 1) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++) {
+        const GsAdamTensor& t = tensors[k];
+        if (t.n < 0 || (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) return GS_E_BAD_ARG;
+    }
+    if (n_tensors == 0) return GS_OK;
+    return launch_adam(n_tensors, tensors, beta1, beta2, eps, step, (hipStream_t)stream);
+}
+
+// ---- the converter's optimizer step: every argument check comes before the first HIP call
+#define GS_OPTIM_MAX_N ((int64_t)1 << 41)  // chunks of 2048 elements are counted in an int
+static int grad_tensors_ok(int32_t n_tensors, const GsGradTensor* tensors) {
+    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n < 0 || (tensors[k].n > 0 && !tensors[k].grad)) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
+    return GS_OK;
+}
+int gs_grad_norm_workspace_bytes(int32_t n_tensors, const GsGradTensor* tensors, size_t* out) {
+    if (!out) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    *out = grad_norm_workspace_bytes(n_tensors, tensors);
+    return GS_OK;
+}
+int gs_grad_norm(int32_t n_tensors, const GsGradTensor* tensors, float max_norm, float* out, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    if (!out || !workspace || !(max_norm >= 0.f)) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    if (workspace_bytes < grad_norm_workspace_bytes(n_tensors, tensors)) return GS_E_WORKSPACE;
+    if (n_tensors == 0) return GS_OK;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_grad_norm(n_tensors, tensors, max_norm, out, (float*)workspace, (hipStream_t)stream);
+}
+int gs_grad_scale(int32_t n_tensors, const GsGradTensor* tensors, const float* clip_coef, void* stream) {
+    if (!clip_coef) return GS_E_BAD_ARG;
+    if (const int rc = grad_tensors_ok(n_tensors, tensors)) return rc;
+    if (n_tensors == 0) return GS_OK;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_grad_scale(n_tensors, tensors, clip_coef, (hipStream_t)stream);
+}
+int gs_adam_step_ex(int32_t n_tensors, const GsAdamTensorEx* tensors, double beta1, double beta2, double eps, int64_t step,
+                    const float* clip_coef, void* stream) {
+    if (n_tensors < 0 || n_tensors > GS_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors)) return GS_E_BAD_ARG;
+    bool host_step = false;
+    for (int k = 0; k < n_tensors; k++) {
+        const GsAdamTensorEx& t = tensors[k];
+        if (t.n < 0 || (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) return GS_E_BAD_ARG;
+        if (!t.step) host_step = true;
+    }
+    if (host_step && step < 1) return GS_E_BAD_ARG;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n >= GS_OPTIM_MAX_N) return GS_E_TOO_LARGE;
+    if (n_tensors == 0) return GS_OK;
+    // (a host step number under capture: a replay would repeat the captured step's bias correction)
+    GS_CAPTURE_OK_IF(stream, !host_step);
+    return launch_adam_ex(n_tensors, tensors, beta1, beta2, eps, host_step ? step : 0, clip_coef, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -49,6 +49,7 @@
 // The launch boundary between the first two is the only cross-workgroup hand-off: no ticket, no grid barrier, no
 // atomics, no memset.  Every gradient is bitwise reproducible and the calls are capture-safe.
 #include "common.h"
+#include "boundary.h"
 
 #define POSE_BONES GS_POSE_BONES
 #define POSE_THREADS 256
@@ -69,7 +70,7 @@ static inline int pose_blocks(int V) {
     const int b = (V + POSE_THREADS - 1) / POSE_THREADS;
     return b < POSE_MAX_BLOCKS ? b : POSE_MAX_BLOCKS;
 }
-size_t pose_workspace_bytes(int V) { return (size_t)pose_blocks(V) * 9 * sizeof(double); }
+static size_t pose_workspace_bytes(int V) { return (size_t)pose_blocks(V) * 9 * sizeof(double); }
 
 // ---- the statistics of the shaped template
 __global__ __launch_bounds__(POSE_THREADS) void pose_stats_kernel(int V, int NB, const float* __restrict__ v_template,
@@ -447,8 +448,8 @@ __global__ __launch_bounds__(POSE_WAVE) void pose_bwd_kernel(PoseTree tree, int 
 }
 
 // ---- launchers (the C ABI has checked every argument)
-int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone, float* loss, float* state, void* workspace,
-                        hipStream_t s) {
+static int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone, float* loss, float* state, void* workspace,
+                               hipStream_t s) {
     StageScope st("pose", s);
     PoseTree tree;
     for (int i = 0; i < POSE_BONES; i++) tree.p[i] = a->parents[i];
@@ -463,9 +464,9 @@ int launch_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bo
     GS_LAUNCH_CHECK("pose", 0, s);
     return GS_OK;
 }
-int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g_rots, const float* g_Jtrs, const float* g_bone,
-                         const float* g_loss, float* dbetas, float* droot, float* dbody, float* dhand, float* dtrans,
-                         hipStream_t s) {
+static int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g_rots, const float* g_Jtrs, const float* g_bone,
+                                const float* g_loss, float* dbetas, float* droot, float* dbody, float* dhand, float* dtrans,
+                                hipStream_t s) {
     StageScope st("pose_bwd", s);
     PoseTree tree;
     for (int i = 0; i < POSE_BONES; i++) tree.p[i] = a->parents[i];
@@ -474,3 +475,47 @@ int launch_pose_backward(const GsPoseArgs* a, const float* state, const float* g
     GS_LAUNCH_CHECK("pose_bwd", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+static int pose_validate(const GsPoseArgs* a) {
+    if (!a || a->V < 1 || a->NB < 1 || a->NB > GS_POSE_MAX_BETAS) return GS_E_BAD_ARG;
+    for (int i = 1; i < GS_POSE_BONES; i++)
+        if (a->parents[i] < 0 || a->parents[i] >= i) return GS_E_BAD_ARG;
+    if (!required(a->J_shapedirs, 4) || !required(a->root_orient, 4) || !required(a->pose_body, 4) || !required(a->pose_hand, 4) ||
+        !aligned(a->rots_gt, 4))
+        return GS_E_BAD_ARG;
+    return GS_OK;
+}
+int gs_pose_workspace_bytes(int32_t V, size_t* out) {
+    if (!out || V < 1) return GS_E_BAD_ARG;
+    *out = pose_workspace_bytes(V);
+    return GS_OK;
+}
+int gs_pose_forward(const GsPoseArgs* a, float* rots, float* Jtrs, float* bone_transforms, float* loss_pose, float* state,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = pose_validate(a)) return rc;
+    if (!required(a->v_template, 4) || !required(a->shapedirs, 4) || !required(a->J_template, 4) || !required(a->betas, 4) ||
+        !required(a->trans, 4) || !required(rots, 4) || !required(Jtrs, 4) || !required(bone_transforms, 4) || !required(state, 4) ||
+        !aligned(loss_pose, 4) || (a->rots_gt && !loss_pose))
+        return GS_E_BAD_ARG;
+    if (!required(workspace, 8)) return GS_E_BAD_ARG;
+    if (workspace_bytes < pose_workspace_bytes(a->V)) return GS_E_WORKSPACE;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_pose_forward(a, rots, Jtrs, bone_transforms, loss_pose, state, workspace, (hipStream_t)stream);
+}
+int gs_pose_backward(const GsPoseArgs* a, const float* state, const float* dL_drots, const float* dL_dJtrs,
+                     const float* dL_dbone_transforms, const float* dL_dloss_pose, float* dL_dbetas, float* dL_droot_orient,
+                     float* dL_dpose_body, float* dL_dpose_hand, float* dL_dtrans, void* stream) {
+    if (const int rc = pose_validate(a)) return rc;
+    if (!required(state, 4) || !aligned(dL_drots, 4) || !aligned(dL_dJtrs, 4) || !aligned(dL_dbone_transforms, 4) ||
+        !aligned(dL_dloss_pose, 4) || !aligned(dL_dbetas, 4) || !aligned(dL_droot_orient, 4) || !aligned(dL_dpose_body, 4) ||
+        !aligned(dL_dpose_hand, 4) || !aligned(dL_dtrans, 4))
+        return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!dL_dbetas && !dL_droot_orient && !dL_dpose_body && !dL_dpose_hand && !dL_dtrans) return GS_OK;
+    return launch_pose_backward(a, state, dL_drots, dL_dJtrs, dL_dbone_transforms, dL_dloss_pose, dL_dbetas, dL_droot_orient,
+                                dL_dpose_body, dL_dpose_hand, dL_dtrans, (hipStream_t)stream);
+}
+
+}  // extern "C"

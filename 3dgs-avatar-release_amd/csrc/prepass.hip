@@ -9,6 +9,7 @@
 //     view-noise matrix, normalised with +1e-12, eval_sh, +0.5, clamp at 0).
 // The reference spends ~10 small torch launches on each and as many again in autograd.
 #include "common.h"
+#include "boundary.h"
 #include "gs_math.h"
 
 // normalised quaternion -> R, as utils/general_utils.py:87-108
@@ -239,34 +240,75 @@ static Mat3 mat3_of(const float* m) {
     return r;
 }
 
-int launch_build_cov(int N, const float* scales, float mod, const float* rot, int is_matrix, float* cov6, hipStream_t s) {
+static int launch_build_cov(int N, const float* scales, float mod, const float* rot, int is_matrix, float* cov6, hipStream_t s) {
     StageScope st("build_cov", s);
     hipLaunchKernelGGL(build_cov_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, scales, mod, rot, is_matrix, cov6);
     GS_LAUNCH_CHECK("build_cov", 0, s);
     return GS_OK;
 }
-int launch_build_cov_bwd(int N, const float* scales, float mod, const float* rot, int is_matrix, const float* dL_dcov6,
-                         float* dL_dscales, float* dL_drot, hipStream_t s) {
+static int launch_build_cov_bwd(int N, const float* scales, float mod, const float* rot, int is_matrix, const float* dL_dcov6,
+                                float* dL_dscales, float* dL_drot, hipStream_t s) {
     StageScope st("build_cov_bwd", s);
     hipLaunchKernelGGL(build_cov_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, scales, mod, rot, is_matrix, dL_dcov6,
                        dL_dscales, dL_drot);
     GS_LAUNCH_CHECK("build_cov_bwd", 0, s);
     return GS_OK;
 }
-int launch_sh2rgb(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
-                  const float* noise_host, float* colors, uint8_t* clamped, hipStream_t s) {
+static int launch_sh2rgb(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
+                         const float* noise_host, float* colors, uint8_t* clamped, hipStream_t s) {
     StageScope st("sh2rgb", s);
     hipLaunchKernelGGL(sh2rgb_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, deg, M, shs, xyz, campos, R_fwd,
                        noise_host ? 1 : 0, mat3_of(noise_host), colors, clamped);
     GS_LAUNCH_CHECK("sh2rgb", 0, s);
     return GS_OK;
 }
-int launch_sh2rgb_bwd(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
-                      const float* noise_host, const uint8_t* clamped, const float* dL_dcolors, float* dL_dshs, float* dL_dxyz,
-                      hipStream_t s) {
+static int launch_sh2rgb_bwd(int N, int deg, int M, const float* shs, const float* xyz, const float* campos, const float* R_fwd,
+                             const float* noise_host, const uint8_t* clamped, const float* dL_dcolors, float* dL_dshs, float* dL_dxyz,
+                             hipStream_t s) {
     StageScope st("sh2rgb_bwd", s);
     hipLaunchKernelGGL(sh2rgb_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, deg, M, shs, xyz, campos, R_fwd,
                        noise_host ? 1 : 0, mat3_of(noise_host), clamped, dL_dcolors, dL_dshs, dL_dxyz);
     GS_LAUNCH_CHECK("sh2rgb_bwd", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+int gs_build_covariance(int32_t N, const float* scaling, float scaling_modifier, const float* rotation, int32_t rotation_is_matrix,
+                        float* cov6, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (N > 0 && (!scaling || !rotation || !cov6))) return GS_E_BAD_ARG;
+    if (!rotation_is_matrix && !aligned(rotation, 16)) return GS_E_BAD_ARG;  // quaternions are read as float4
+    if (N == 0) return GS_OK;
+    return launch_build_cov(N, scaling, scaling_modifier, rotation, rotation_is_matrix ? 1 : 0, cov6, (hipStream_t)stream);
+}
+int gs_build_covariance_backward(int32_t N, const float* scaling, float scaling_modifier, const float* rotation,
+                                 int32_t rotation_is_matrix, const float* dL_dcov6, float* dL_dscaling, float* dL_drotation,
+                                 void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (N > 0 && (!scaling || !rotation || !dL_dcov6 || !dL_dscaling || !dL_drotation))) return GS_E_BAD_ARG;
+    if (!rotation_is_matrix && (!aligned(rotation, 16) || !aligned(dL_drotation, 16))) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_build_cov_bwd(N, scaling, scaling_modifier, rotation, rotation_is_matrix ? 1 : 0, dL_dcov6, dL_dscaling,
+                                dL_drotation, (hipStream_t)stream);
+}
+int gs_sh2rgb(int32_t N, int32_t sh_degree, int32_t M, const float* shs, const float* xyz, const float* campos,
+              const float* fwd_rotation, const float* view_noise_host, float* colors, uint8_t* clamped, void* stream) {
+    GS_CAPTURE_OK_IF(stream, view_noise_host == nullptr);  // (a host matrix would be baked into the graph)
+    if (N < 0 || sh_degree < 0 || sh_degree > 3 || M < (sh_degree + 1) * (sh_degree + 1) || M > 16) return GS_E_BAD_ARG;
+    if (N > 0 && (!shs || !xyz || !campos || !colors || !clamped)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_sh2rgb(N, sh_degree, M, shs, xyz, campos, fwd_rotation, view_noise_host, colors, clamped, (hipStream_t)stream);
+}
+int gs_sh2rgb_backward(int32_t N, int32_t sh_degree, int32_t M, const float* shs, const float* xyz, const float* campos,
+                       const float* fwd_rotation, const float* view_noise_host, const uint8_t* clamped,
+                       const float* dL_dcolors, float* dL_dshs, float* dL_dxyz, void* stream) {
+    GS_CAPTURE_OK_IF(stream, view_noise_host == nullptr);
+    if (N < 0 || sh_degree < 0 || sh_degree > 3 || M < (sh_degree + 1) * (sh_degree + 1) || M > 16) return GS_E_BAD_ARG;
+    if (N > 0 && (!shs || !xyz || !campos || !clamped || !dL_dcolors || !dL_dshs || !dL_dxyz)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    return launch_sh2rgb_bwd(N, sh_degree, M, shs, xyz, campos, fwd_rotation, view_noise_host, clamped, dL_dcolors, dL_dshs,
+                             dL_dxyz, (hipStream_t)stream);
+}
+
+}  // extern "C"

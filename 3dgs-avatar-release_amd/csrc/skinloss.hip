@@ -37,10 +37,11 @@
 //   skin_loss_bwd      recomputes W and writes every dlogits row once.
 // No atomics, no memsets, no host reads: every result is bitwise reproducible, and the calls are capture-safe.
 #include "common.h"
+#include "boundary.h"
 #include "skin_act.h"
 
 static inline int skinloss_blocks(int n) { return (n + SKIN_THREADS - 1) / SKIN_THREADS; }
-size_t skin_loss_workspace_bytes(int n) { return (size_t)skinloss_blocks(n) * sizeof(double); }
+static size_t skin_loss_workspace_bytes(int n) { return (size_t)skinloss_blocks(n) * sizeof(double); }
 
 __device__ __forceinline__ int clamp_vertex(int i, int V) { return min(max(i, 0), V - 1); }
 
@@ -210,17 +211,17 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_loss_bwd_kernel(int n, cons
 }
 
 // ---- launchers (the C ABI has checked every argument; n > 0)
-int launch_mesh_sample(int n, int V, int F, const float* verts, const int* faces, const float* cdf, const float* vweights,
-                       const float* aabb_min, const float* aabb_inv_extent, const float* draws, float* p_norm, float* target,
-                       int* face, float* bary, float* points, hipStream_t s) {
+static int launch_mesh_sample(int n, int V, int F, const float* verts, const int* faces, const float* cdf, const float* vweights,
+                              const float* aabb_min, const float* aabb_inv_extent, const float* draws, float* p_norm, float* target,
+                              int* face, float* bary, float* points, hipStream_t s) {
     StageScope st("skin_sample", s);
     hipLaunchKernelGGL(skin_sample_kernel, dim3(skinloss_blocks(n)), dim3(SKIN_THREADS), 0, s, n, V, F, verts, faces, cdf,
                        vweights, aabb_min, aabb_inv_extent, draws, p_norm, target, face, bary, points);
     GS_LAUNCH_CHECK("skin_sample", 0, s);
     return GS_OK;
 }
-int launch_skin_loss_forward(int n, int kind, const float* logits, const float* target, float* loss, void* workspace,
-                             hipStream_t s) {
+static int launch_skin_loss_forward(int n, int kind, const float* logits, const float* target, float* loss, void* workspace,
+                                    hipStream_t s) {
     StageScope st("skin_loss", s);
     const int nb = skinloss_blocks(n);
     double* partial = reinterpret_cast<double*>(workspace);
@@ -234,8 +235,8 @@ int launch_skin_loss_forward(int n, int kind, const float* logits, const float* 
     GS_LAUNCH_CHECK("skin_loss_final", 0, s);
     return GS_OK;
 }
-int launch_skin_loss_backward(int n, int kind, const float* logits, const float* target, const float* dL_dloss,
-                              float* dL_dlogits, hipStream_t s) {
+static int launch_skin_loss_backward(int n, int kind, const float* logits, const float* target, const float* dL_dloss,
+                                     float* dL_dlogits, hipStream_t s) {
     StageScope st("skin_loss_bwd", s);
     const int nb = skinloss_blocks(n);
     if (kind == GS_SKIN_HIERARCHICAL)
@@ -247,3 +248,45 @@ int launch_skin_loss_backward(int n, int kind, const float* logits, const float*
     GS_LAUNCH_CHECK("skin_loss_bwd", 0, s);
     return GS_OK;
 }
+
+extern "C" {
+
+static bool skin_loss_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX; }
+int gs_mesh_sample(int32_t n, int32_t V, int32_t F, const float* verts, const int32_t* faces, const float* cdf,
+                   const float* vweights, const float* aabb_min, const float* aabb_inv_extent, const float* draws,
+                   float* points_norm, float* target, int32_t* face, float* bary, float* points, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || V < 1 || F < 1) return GS_E_BAD_ARG;
+    if (!required(verts, 4) || !required(faces, 4) || !required(cdf, 4) || !required(vweights, 16) || !required(aabb_min, 4) ||
+        !required(aabb_inv_extent, 4))
+        return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!required(draws, 4) || !required(points_norm, 16) || !required(target, 16)) return GS_E_BAD_ARG;
+    if (!aligned(face, 4) || !aligned(bary, 16) || !aligned(points, 16)) return GS_E_BAD_ARG;
+    return launch_mesh_sample(n, V, F, verts, faces, cdf, vweights, aabb_min, aabb_inv_extent, draws, points_norm, target, face,
+                              bary, points, (hipStream_t)stream);
+}
+int gs_skin_loss_workspace_bytes(int32_t n, size_t* out) {
+    if (!out || n < 0) return GS_E_BAD_ARG;
+    *out = skin_loss_workspace_bytes(n);
+    return GS_OK;
+}
+int gs_skin_loss_forward(int32_t n, int32_t kind, const float* logits, const float* target, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!required(logits, 16) || !required(target, 16) || !required(loss, 4) || !required(workspace, 16)) return GS_E_BAD_ARG;
+    if (workspace_bytes < skin_loss_workspace_bytes(n)) return GS_E_WORKSPACE;
+    return launch_skin_loss_forward(n, kind, logits, target, loss, workspace, (hipStream_t)stream);
+}
+int gs_skin_loss_backward(int32_t n, int32_t kind, const float* logits, const float* target, const float* dL_dloss,
+                          float* dL_dlogits, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (n < 0 || !skin_loss_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (n == 0) return GS_OK;
+    if (!required(logits, 16) || !required(target, 16) || !required(dL_dloss, 4) || !required(dL_dlogits, 16)) return GS_E_BAD_ARG;
+    return launch_skin_loss_backward(n, kind, logits, target, dL_dloss, dL_dlogits, (hipStream_t)stream);
+}
+
+}  // extern "C"

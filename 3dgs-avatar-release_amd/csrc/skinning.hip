@@ -44,6 +44,7 @@
 // 16-byte aligned.  No atomics, no memsets: every gradient is bitwise reproducible, and the calls are capture-safe.
 // The activations, their reverses and the slab moves are in skin_act.h, which skinloss.hip shares.
 #include "common.h"
+#include "boundary.h"
 #include "gs_math.h"
 #include "skin_act.h"
 
@@ -52,7 +53,7 @@
 #define SKIN_THIRD 86   // rows of one third of a block (the last has 84)
 
 static inline int skin_blocks(int N) { return (N + SKIN_THREADS - 1) / SKIN_THREADS; }
-size_t skinning_workspace_bytes(int N) { return (size_t)skin_blocks(N) * (SKIN_BONES * 12) * sizeof(double); }
+static size_t skinning_workspace_bytes(int N) { return (size_t)skin_blocks(N) * (SKIN_BONES * 12) * sizeof(double); }
 
 // ---- the activation alone
 template <int KIND>
@@ -328,31 +329,31 @@ __global__ __launch_bounds__(64) void skin_dtfs_reduce_kernel(int nb, const doub
         default: hipLaunchKernelGGL(KERNEL<GS_SKIN_WEIGHTS>, __VA_ARGS__); break;                                  \
     }
 
-int launch_skin_weights_forward(int N, int kind, const float* logits, float* weights, hipStream_t s) {
+static int launch_skin_weights_forward(int N, int kind, const float* logits, float* weights, hipStream_t s) {
     StageScope st("skin_weights", s);
     SKIN_DISPATCH(kind, skin_weights_fwd_kernel, dim3(skin_blocks(N)), dim3(SKIN_THREADS), 0, s, N, logits, weights)
     GS_LAUNCH_CHECK("skin_weights", 0, s);
     return GS_OK;
 }
-int launch_skin_weights_backward(int N, int kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
-                                 hipStream_t s) {
+static int launch_skin_weights_backward(int N, int kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
+                                        hipStream_t s) {
     StageScope st("skin_weights_bwd", s);
     SKIN_DISPATCH(kind, skin_weights_bwd_kernel, dim3(skin_blocks(N)), dim3(SKIN_THREADS), 0, s, N, logits, dL_dweights,
                   dL_dlogits)
     GS_LAUNCH_CHECK("skin_weights_bwd", 0, s);
     return GS_OK;
 }
-int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
-                            float* xyz_out, float* rot_out, float* T_fwd, hipStream_t s) {
+static int launch_skinning_forward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
+                                   float* xyz_out, float* rot_out, float* T_fwd, hipStream_t s) {
     StageScope st("skinning", s);
     SKIN_DISPATCH(kind, skin_fwd_kernel, dim3(skin_blocks(N)), dim3(SKIN_THREADS), 0, s, N, w, tfs, xyz, rot, xyz_out, rot_out,
                   T_fwd)
     GS_LAUNCH_CHECK("skinning", 0, s);
     return GS_OK;
 }
-int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
-                             const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
-                             void* workspace, hipStream_t s) {
+static int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, const float* xyz, const float* rot,
+                                    const float* dxyz_out, const float* drot_out, float* dw, float* dtfs, float* dxyz, float* drot,
+                                    void* workspace, hipStream_t s) {
     StageScope st("skinning_bwd", s);
     const int nb = skin_blocks(N);
     double* partial = dtfs ? reinterpret_cast<double*>(workspace) : nullptr;
@@ -365,3 +366,57 @@ int launch_skinning_backward(int N, int kind, const float* w, const float* tfs, 
     }
     return GS_OK;
 }
+
+extern "C" {
+
+static bool skin_kind_ok(int32_t kind) { return kind == GS_SKIN_HIERARCHICAL || kind == GS_SKIN_SOFTMAX || kind == GS_SKIN_WEIGHTS; }
+int gs_skin_weights_forward(int32_t N, int32_t kind, const float* logits, float* weights, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!required(logits, 16) || !required(weights, 16)) return GS_E_BAD_ARG;
+    return launch_skin_weights_forward(N, kind, logits, weights, (hipStream_t)stream);
+}
+int gs_skin_weights_backward(int32_t N, int32_t kind, const float* logits, const float* dL_dweights, float* dL_dlogits,
+                             void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || (kind != GS_SKIN_HIERARCHICAL && kind != GS_SKIN_SOFTMAX)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!required(logits, 16) || !required(dL_dweights, 16) || !required(dL_dlogits, 16)) return GS_E_BAD_ARG;
+    return launch_skin_weights_backward(N, kind, logits, dL_dweights, dL_dlogits, (hipStream_t)stream);
+}
+int gs_skinning_workspace_bytes(int32_t N, size_t* out) {
+    if (!out || N < 0) return GS_E_BAD_ARG;
+    *out = skinning_workspace_bytes(N);
+    return GS_OK;
+}
+int gs_skinning_forward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                        float* xyz_out, float* rotation_out, float* T_fwd, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!required(w, 16) || !required(tfs, 16) || !required(xyz, 4) || !required(rotation, 16) || !required(xyz_out, 16) ||
+        !required(rotation_out, 16) || !required(T_fwd, 16))
+        return GS_E_BAD_ARG;
+    return launch_skinning_forward(N, kind, w, tfs, xyz, rotation, xyz_out, rotation_out, T_fwd, (hipStream_t)stream);
+}
+int gs_skinning_backward(int32_t N, int32_t kind, const float* w, const float* tfs, const float* xyz, const float* rotation,
+                         const float* dL_dxyz_out, const float* dL_drotation_out, float* dL_dw, float* dL_dtfs,
+                         float* dL_dxyz, float* dL_drotation, void* workspace, size_t workspace_bytes, void* stream) {
+    GS_CAPTURE_OK_IF(stream, true);
+    if (N < 0 || !skin_kind_ok(kind)) return GS_E_BAD_ARG;
+    if (N == 0) return GS_OK;
+    if (!required(w, 16) || !required(tfs, 16) || !required(xyz, 4) || !required(rotation, 16)) return GS_E_BAD_ARG;
+    if (!aligned(dL_dxyz_out, 4) || !aligned(dL_drotation_out, 4) || !aligned(dL_dw, 16) || !aligned(dL_dtfs, 4) ||
+        !aligned(dL_dxyz, 4) || !aligned(dL_drotation, 16))
+        return GS_E_BAD_ARG;
+    if (dL_dtfs) {
+        if (!required(workspace, 16)) return GS_E_BAD_ARG;
+        if (workspace_bytes < skinning_workspace_bytes(N)) return GS_E_WORKSPACE;
+    }
+    if (!dL_dw && !dL_dtfs && !dL_dxyz && !dL_drotation) return GS_OK;
+    return launch_skinning_backward(N, kind, w, tfs, xyz, rotation, dL_dxyz_out, dL_drotation_out, dL_dw, dL_dtfs, dL_dxyz,
+                                    dL_drotation, workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -46,6 +46,7 @@
 //   The partition of the rows into partials depends on N, D and Lt alone -- never on the device.  No atomics, no memsets, no
 //   host synchronisation, no host memory traffic: every gradient is bitwise reproducible and the calls are capture-safe.
 #include "common.h"
+#include "boundary.h"
 #include "gs_math.h"
 
 #define TX_THREADS 256
@@ -68,9 +69,14 @@ static inline int tx_blocks(int N, int D) {
     const int R = tx_rows(D);
     return (N + R - 1) / R;
 }
-size_t texture_workspace_bytes(int N, int D, int latent_dim) {
+static size_t texture_workspace_bytes(int N, int D, int latent_dim) {
     return (size_t)latent_dim * tx_blocks(N, D) * sizeof(float);
 }
+// the block gradients' addresses, passed to the backward kernel by value
+struct TxGrads {
+    float* before[GS_TEXTURE_MAX_BEFORE];
+    float* after[GS_TEXTURE_MAX_AFTER];
+};
 
 // n rows of a contiguous (., w) block at src (16-byte aligned) -> columns [col, col + w) of the slab in LDS
 __device__ __forceinline__ void tx_scatter(float* buf, int D, int col, const float* __restrict__ src, int n, int w) {
@@ -323,14 +329,14 @@ __global__ __launch_bounds__(TX_THREADS) void tx_final_kernel(const float* __res
 }
 
 // ---- launchers (the C ABI has checked every argument)
-int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s) {
+static int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s) {
     StageScope st("texture_input", s);
     hipLaunchKernelGGL(tx_input_fwd_kernel, dim3(tx_blocks(a->N, a->D)), dim3(TX_THREADS), 0, s, *a, tx_rows(a->D), inp);
     GS_LAUNCH_CHECK("texture_input", 0, s);
     return GS_OK;
 }
-int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const TxGrads& grads, float* dxyz, float* dlatent,
-                                  void* workspace, hipStream_t s) {
+static int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const TxGrads& grads, float* dxyz, float* dlatent,
+                                         void* workspace, hipStream_t s) {
     StageScope st("texture_input_bwd", s);
     const int nb = tx_blocks(a->N, a->D);
     float* partial = dlatent ? reinterpret_cast<float*>(workspace) : nullptr;
@@ -342,3 +348,73 @@ int launch_texture_input_backward(const GsTextureArgs* a, const float* g, const 
     }
     return GS_OK;
 }
+
+extern "C" {
+
+static int texture_validate(const GsTextureArgs* a) {
+    if (!a || a->N < 0 || a->sh_degree < 0 || a->sh_degree > 4 || a->n_before < 0 || a->n_before > GS_TEXTURE_MAX_BEFORE ||
+        a->n_after < 0 || a->n_after > GS_TEXTURE_MAX_AFTER || a->latent_dim < 0 || a->latent_dim > GS_TEXTURE_MAX_D)
+        return GS_E_BAD_ARG;
+    int64_t sum = (a->sh_degree + 1) * (a->sh_degree + 1) - 1 + a->latent_dim;
+    for (int b = 0; b < a->n_before; b++) {
+        if (a->before_w[b] < 1 || a->before_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
+        sum += a->before_w[b];
+    }
+    for (int b = 0; b < a->n_after; b++) {
+        if (a->after_w[b] < 1 || a->after_w[b] > GS_TEXTURE_MAX_D) return GS_E_BAD_ARG;
+        sum += a->after_w[b];
+    }
+    if (a->D < 1 || a->D > GS_TEXTURE_MAX_D || sum != a->D) return GS_E_BAD_ARG;
+    return GS_OK;
+}
+// what the view direction is made of (sh_degree > 0)
+static bool texture_dir_ok(const GsTextureArgs* a) {
+    if (!required(a->xyz, 4) || !required(a->campos, 4) || !aligned(a->fwd_transform, 4)) return false;
+    return !a->fwd_transform || (a->rot_row >= 3 && a->rot_stride >= 2 * (int64_t)a->rot_row + 3);
+}
+int gs_texture_workspace_bytes(int32_t N, int32_t D, int32_t latent_dim, size_t* out) {
+    if (!out || N < 0 || D < 1 || D > GS_TEXTURE_MAX_D || latent_dim < 0 || latent_dim > D) return GS_E_BAD_ARG;
+    *out = texture_workspace_bytes(N, D, latent_dim);
+    return GS_OK;
+}
+int gs_texture_input_forward(const GsTextureArgs* a, float* inp, void* stream) {
+    if (const int rc = texture_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!required(inp, 16)) return GS_E_BAD_ARG;
+    for (int b = 0; b < a->n_before; b++)
+        if (!required(a->before[b], 16)) return GS_E_BAD_ARG;
+    for (int b = 0; b < a->n_after; b++)
+        if (!required(a->after[b], 16)) return GS_E_BAD_ARG;
+    if (a->latent_dim > 0 && !required(a->latent, 4)) return GS_E_BAD_ARG;
+    if (a->sh_degree > 0 && !texture_dir_ok(a)) return GS_E_BAD_ARG;
+    GS_CAPTURE_OK_IF(stream, true);
+    return launch_texture_input_forward(a, inp, (hipStream_t)stream);
+}
+int gs_texture_input_backward(const GsTextureArgs* a, const float* dL_dinp, float* const* dL_dbefore, float* const* dL_dafter,
+                              float* dL_dxyz, float* dL_dlatent, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = texture_validate(a)) return rc;
+    if (a->N == 0) return GS_OK;
+    if (!required(dL_dinp, 16)) return GS_E_BAD_ARG;
+    TxGrads gr = {};
+    bool any = dL_dxyz || dL_dlatent;
+    for (int b = 0; b < a->n_before; b++) {
+        gr.before[b] = dL_dbefore ? dL_dbefore[b] : nullptr;
+        if (!aligned(gr.before[b], 16)) return GS_E_BAD_ARG;
+        any = any || gr.before[b];
+    }
+    for (int b = 0; b < a->n_after; b++) {
+        gr.after[b] = dL_dafter ? dL_dafter[b] : nullptr;
+        if (!aligned(gr.after[b], 16)) return GS_E_BAD_ARG;
+        any = any || gr.after[b];
+    }
+    if (dL_dxyz && (a->sh_degree == 0 || !aligned(dL_dxyz, 4) || !texture_dir_ok(a))) return GS_E_BAD_ARG;
+    if (dL_dlatent) {
+        if (a->latent_dim == 0 || !aligned(dL_dlatent, 4) || !required(workspace, 4)) return GS_E_BAD_ARG;
+        if (workspace_bytes < texture_workspace_bytes(a->N, a->D, a->latent_dim)) return GS_E_WORKSPACE;
+    }
+    GS_CAPTURE_OK_IF(stream, true);
+    if (!any) return GS_OK;
+    return launch_texture_input_backward(a, dL_dinp, gr, dL_dxyz, dL_dlatent, workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -430,6 +430,23 @@ def ptr(t):
     return t.data_ptr()
 
 
+_float32 = None
+
+
+def dev32(t, name):
+    """`t` itself, after the two checks the fused modules make of a tensor argument: on the GPU, fp32.  (The caller detaches
+    it or makes it contiguous, as its kernels need.)"""
+    global _float32
+    if _float32 is None:
+        import torch
+        _float32 = torch.float32
+    if not t.is_cuda:
+        raise RuntimeError("%s must live on the GPU (the fused HIP kernels have no CPU fallback)" % name)
+    if t.dtype != _float32:
+        raise TypeError("%s: fp32 tensor expected" % name)
+    return t
+
+
 def is_aligned(t, nbytes=16):
     """True when `t.data_ptr()` is a multiple of `nbytes` (an empty tensor counts as aligned: it is passed as NULL).  A
     contiguous view can start at any element of its storage (`img[1:]` of a (3, H, W) image with H W odd starts 4 bytes

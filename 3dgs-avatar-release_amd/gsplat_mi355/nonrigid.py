@@ -29,11 +29,7 @@ ROT_OFFSETS = {"add": _lib.GS_NR_ROT_ADD, "mult": _lib.GS_NR_ROT_MULT}
 
 
 def _dev32(t, name):
-    if not t.is_cuda:
-        raise RuntimeError("%s must live on the GPU (the fused HIP kernels have no CPU fallback)" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s: fp32 tensor expected" % name)
-    return t.detach()
+    return _lib.dev32(t, name).detach()
 
 
 # ---- the pose encoder

@@ -15,11 +15,7 @@ from . import _lib
 
 
 def _dev32(t, name):
-    if not t.is_cuda:
-        raise RuntimeError("%s must live on the GPU (the fused HIP kernels have no CPU fallback)" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s: fp32 tensor expected" % name)
-    return t.contiguous()
+    return _lib.dev32(t, name).contiguous()
 
 
 def _stream(dev):

@@ -29,11 +29,7 @@ BONES = _lib.GS_SKIN_BONES
 
 
 def _dev32(t, name):
-    if not t.is_cuda:
-        raise RuntimeError("%s must live on the GPU (the fused HIP kernels have no CPU fallback)" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s: fp32 tensor expected" % name)
-    return t.detach()
+    return _lib.dev32(t, name).detach()
 
 
 def _logit_kind(w, weights):
