@@ -102,6 +102,12 @@ __global__ __launch_bounds__(256) void segment_reduce_kernel(int P, const int32_
     }
 }
 
+// One instantiation per value of GsFwdArgs.antialiasing, chosen by the host (launch_gaussian_backward).  This file is compiled
+// with FMA contraction, which the compiler applies within a basic block: a run-time `if (antialiasing)` in the covariance
+// chain -- or the two bodies behind one branch of a common kernel: both were measured -- changes which products fuse with
+// which sums, and the default path's gradients then differ from what they were in their last bits.  As a compile-time
+// constant the flag leaves the instantiation for 0 the kernel it was without the option, instruction for instruction.
+template <bool antialiasing>
 __global__ __launch_bounds__(256) void gaussian_bwd_kernel(
     int P, int deg, int M, const float* __restrict__ means3D, const float* __restrict__ scales, float scale_modifier,
     const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
@@ -109,7 +115,8 @@ __global__ __launch_bounds__(256) void gaussian_bwd_kernel(
     int H, float tanfovx, float tanfovy, float fx, float fy, const int32_t* __restrict__ radii,
     const uint32_t* __restrict__ clamped, const float4* __restrict__ sums, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D,
     float* __restrict__ dL_dsh, float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity,
-    float* __restrict__ dL_dscales, float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D) {
+    float* __restrict__ dL_dscales, float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D,
+    const float4* __restrict__ rec) {
     extern __shared__ float sh_tile[];  // SH rows of this workgroup: coefficients in, gradients out (in place)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int ld = sh_tile_ld(M);
@@ -166,8 +173,11 @@ __global__ __launch_bounds__(256) void gaussian_bwd_kernel(
             cov3d_from_scale_rot(sc, scale_modifier, q, c6);
         }
         // (i) conic -> cov2D, (ii) cov2D -> cov3D, (iii) cov2D -> mean through J
-        float cov[3], Mx[2][3], t[3], tt2[2];
-        cov2d(mean, fx, fy, tanfovx, tanfovy, c6, V, cov, Mx, t, tt2);
+        // GsFwdArgs.antialiasing (wave-uniform): the record's opacity is o' = o s (preprocess.hip), so gO is dL/do'; what
+        // the terms below need of the record is requested here, ahead of the projection
+        const float op_eff = antialiasing ? rec[(size_t)i * 3 + 1].y : 0.f;
+        float cov[3], Mx[2][3], t[3], tt2[2], pre[2];
+        cov2d(mean, fx, fy, tanfovx, tanfovy, c6, V, cov, Mx, t, tt2, pre);
         const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
         const float x_grad_mul = (tt2[0] < -limx || tt2[0] > limx) ? 0.f : 1.f;
         const float y_grad_mul = (tt2[1] < -limy || tt2[1] > limy) ? 0.f : 1.f;
@@ -175,10 +185,24 @@ __global__ __launch_bounds__(256) void gaussian_bwd_kernel(
         const float denom = ca * cc - cb * cb;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
         float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+        float aa_det0 = 0.f;
+        bool aa_unclamped = false;
+        if (antialiasing) dL_dopacity[i] = antialias_scale(pre[0], cb, pre[1], denom, &aa_det0, &aa_unclamped) * gO;  // o' = o s
         if (denom2inv != 0.f) {
             dL_da = denom2inv * (-cc * cc * gA + 2 * cb * cc * gB + (denom - ca * cc) * gC);
             dL_dc = denom2inv * (-ca * ca * gC + 2 * ca * cb * gB + (denom - ca * cc) * gA);
             dL_db = denom2inv * 2 * (cb * cc * gA - (denom + 2 * cb * cb) * gB + ca * cb * gC);
+            if (antialiasing && aa_unclamped) {
+                // where the ratio is not clamped, do'/d(a, b, c) = o' (1/2) d ln(det0 / det1), det0 = a0 c0 - b^2 of the
+                // undilated covariance (a = a0 + 0.3: da0 = da), b the one off-diagonal parameter as in dL_db above.
+                // Added here, the terms reach cov3D and the mean (through M = J Rv, under the same x / y masks) with the
+                // conic's
+                const float i0 = 1.0f / aa_det0, i1 = 1.0f / denom;
+                const float w = gO * op_eff;
+                dL_da += w * 0.5f * (pre[1] * i0 - cc * i1);
+                dL_dc += w * 0.5f * (pre[0] * i0 - ca * i1);
+                dL_db += w * cb * (i1 - i0);
+            }
             const float* m0 = Mx[0];
             const float* m1 = Mx[1];
             gc[0] = (m0[0] * m0[0] * dL_da + m0[0] * m1[0] * dL_db + m1[0] * m1[0] * dL_dc);
@@ -345,11 +369,13 @@ int launch_gaussian_backward(const GsFwdArgs& a, const int32_t* radii, const flo
                        reinterpret_cast<const float4*>(qrows), reinterpret_cast<float4*>(sums), marks_flag);
     GS_LAUNCH_CHECK("segment_reduce", a.debug, s);
     const size_t lds = a.shs ? (size_t)GB_THREADS * ((3 * a.M) | 1) * sizeof(float) : 0;
-    hipLaunchKernelGGL(gaussian_bwd_kernel, dim3((a.P + GB_THREADS - 1) / GB_THREADS), dim3(GB_THREADS), lds, s, a.P, a.sh_degree, a.M, a.means3D,
+    hipLaunchKernelGGL(a.antialiasing ? gaussian_bwd_kernel<true> : gaussian_bwd_kernel<false>,
+                       dim3((a.P + GB_THREADS - 1) / GB_THREADS), dim3(GB_THREADS), lds, s, a.P, a.sh_degree, a.M, a.means3D,
                        a.scales, a.scale_modifier, a.rotations, a.shs, a.cov3D_precomp, a.viewmatrix, a.projmatrix,
                        a.campos, a.W, a.H, a.tanfovx, a.tanfovy, fx, fy, radii, clamped,
                        reinterpret_cast<const float4*>(sums), g.dL_dmeans3D, g.dL_dmeans2D,
-                       g.dL_dsh, g.dL_dcolors, g.dL_dopacity, g.dL_dscales, g.dL_drotations, g.dL_dcov3D);
+                       g.dL_dsh, g.dL_dcolors, g.dL_dopacity, g.dL_dscales, g.dL_drotations, g.dL_dcov3D,
+                       reinterpret_cast<const float4*>(rec));
     GS_LAUNCH_CHECK("gaussian_backward", a.debug, s);
     return GS_OK;
 }

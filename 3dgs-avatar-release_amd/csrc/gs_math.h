@@ -79,10 +79,12 @@ __device__ __forceinline__ void cov3d_from_scale_rot(const float3 scale, float m
 }
 
 // EWA projection: cov2D = (J Rv) Sigma (J Rv)^T + 0.3 I.  Outputs cov = (a, b, c), M = J Rv, the
-// clamped view-space point t and the unclamped ratios (t.x/t.z, t.y/t.z) for the backward mask.
+// clamped view-space point t and the unclamped ratios (t.x/t.z, t.y/t.z) for the backward mask.  pre = the two diagonal
+// sums (a0, c0) before 0.3 is added (the antialiasing option's undilated covariance: a - 0.3 would have lost their low
+// bits); cov is the same sum of the same operands as before, bit for bit.
 __device__ __forceinline__ void cov2d(const float3 mean, float fx, float fy, float tanfovx, float tanfovy,
                                       const float* c6, const float* V, float* cov, float M[2][3], float* t_out,
-                                      float* ratios) {
+                                      float* ratios, float* pre) {
     float3 t = xform4x3(mean, V);
     const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
     const float txtz = t.x / t.z, tytz = t.y / t.z;
@@ -101,11 +103,26 @@ __device__ __forceinline__ void cov2d(const float3 mean, float fx, float fy, flo
     for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) MS[i][j] = M[i][0] * S[0][j] + M[i][1] * S[1][j] + M[i][2] * S[2][j];
-    cov[0] = MS[0][0] * M[0][0] + MS[0][1] * M[0][1] + MS[0][2] * M[0][2] + 0.3f;
+    pre[0] = MS[0][0] * M[0][0] + MS[0][1] * M[0][1] + MS[0][2] * M[0][2];
+    pre[1] = MS[1][0] * M[1][0] + MS[1][1] * M[1][1] + MS[1][2] * M[1][2];
+    cov[0] = pre[0] + 0.3f;
     cov[1] = MS[0][0] * M[1][0] + MS[0][1] * M[1][1] + MS[0][2] * M[1][2];
-    cov[2] = MS[1][0] * M[1][0] + MS[1][1] * M[1][1] + MS[1][2] * M[1][2] + 0.3f;
+    cov[2] = pre[1] + 0.3f;
     t_out[0] = t.x; t_out[1] = t.y; t_out[2] = t.z;
     ratios[0] = txtz; ratios[1] = tytz;
+}
+
+// GsFwdArgs.antialiasing: the factor s on a Gaussian's opacity that makes up for the 0.3 px^2 dilation of its footprint,
+// s = sqrt(max(0.000025, det0 / det1)) with det0 = a0 c0 - b^2 of the undilated covariance (cov2d's `pre`) and det1 that of
+// the dilated one.  *unclamped = det0 / det1 > 0.000025 (false also for det0 <= 0 and for a NaN ratio): the backward adds
+// its covariance terms exactly there.  The clamped value is the constant 0.005, not a square root taken on the device.
+#define AA_RATIO_MIN 0.000025f
+#define AA_SCALE_MIN 0.005f
+__device__ __forceinline__ float antialias_scale(float a0, float b, float c0, float det1, float* det0, bool* unclamped) {
+    *det0 = a0 * c0 - b * b;
+    const float r = *det0 / det1;
+    *unclamped = r > AA_RATIO_MIN;
+    return *unclamped ? sqrtf(r) : AA_SCALE_MIN;
 }
 
 // An upper bound of ln(x) for x >= 1 from exactly rounded IEEE operations only (no libm: the tile rectangle it

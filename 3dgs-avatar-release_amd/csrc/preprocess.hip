@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     float* __restrict__ rec, float* __restrict__ depths, uint32_t* __restrict__ tiles, uint32_t* __restrict__ clamped,
     uint32_t* __restrict__ sort_keys, uint32_t* __restrict__ sort_vals, int32_t* __restrict__ radii,
     uint32_t* __restrict__ wave_tiles, uint32_t* __restrict__ wave_kmin, uint32_t* __restrict__ wave_kmax, ZeroJob zero,
-    ZeroJob zero2) {
+    ZeroJob zero2, int antialiasing) {
     zero_job(zero);   // the depth sort's digit totals (saves a fill launch)
     zero_job(zero2);  // the tile binning's per-tile pair totals (its counting pass adds into them)
     // threads past the end (last workgroup only) redo Gaussian P - 1 and store nothing: every lane of every wave reaches
@@ -93,10 +93,19 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
         } else {
             cov3d_from_scale_rot(sc_in, scale_modifier, q_in, c6);
         }
-        float cov[3], Mx[2][3], tcl[3], tt2[2];
-        cov2d(p, focal_x, focal_y, tanfovx, tanfovy, c6, V, cov, Mx, tcl, tt2);
+        float cov[3], Mx[2][3], tcl[3], tt2[2], pre[2];
+        cov2d(p, focal_x, focal_y, tanfovx, tanfovy, c6, V, cov, Mx, tcl, tt2, pre);
         const float det = cov[0] * cov[2] - cov[1] * cov[1];
         if (det != 0.0f) {
+            // GsFwdArgs.antialiasing (wave-uniform): the opacity everything downstream sees -- the snug tile box, the
+            // record the render loops, the backward and a shared-geometry second render read -- is scaled by how much the
+            // 0.3 px^2 dilation inflated the footprint.  Radii, conic, depth, colour and culling do not depend on it.
+            float opacity = opacity_in;
+            if (antialiasing) {
+                float det0;
+                bool unclamped;
+                opacity = opacity_in * antialias_scale(pre[0], cov[1], pre[1], det, &det0, &unclamped);
+            }
             const float det_inv = 1.f / det;
             const float cA = cov[2] * det_inv, cB = -cov[1] * det_inv, cC = cov[0] * det_inv;
             const float mid = 0.5f * (cov[0] + cov[2]);
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
                     // bin into the bounding box of the alpha >= 1/255 region only (GsFwdArgs.tile_rect = 1); the
                     // Gaussian stays "visible" (radii, colour, depth) exactly as with the square
                     float hx, hy;
-                    if (snug_half_widths(opacity_in, cov[0], cov[2], det, &hx, &hy)) {
+                    if (snug_half_widths(opacity, cov[0], cov[2], det, &hx, &hy)) {
                         minx = max(minx, (int)((px - hx) / TILE));
                         miny = max(miny, (int)((py - hy) / TILE));
                         maxx = min(maxx, (int)((px + hx) / TILE) + 1);
@@ -145,7 +154,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
                 radius = r;
                 tt = (uint32_t)(w * h);
                 r0 = make_float4(px, py, cA, cB);
-                r1 = make_float4(cC, opacity_in, col.x, col.y);
+                r1 = make_float4(cC, opacity, col.x, col.y);
                 r2x = col.z;
                 rmin_bits = (uint32_t)minx | ((uint32_t)miny << 16);
                 rsize_bits = (uint32_t)w | ((uint32_t)h << 16);
@@ -193,7 +202,8 @@ int launch_preprocess(const GsFwdArgs& a, float* rec, float* depths, uint32_t* t
                        a.scale_modifier, a.rotations, a.opacities, a.shs, a.colors_precomp, a.cov3D_precomp,
                        a.viewmatrix, a.projmatrix, a.campos, a.W, a.H, a.tanfovx, a.tanfovy, focal_x, focal_y, gx, gy,
                        a.tile_rect,
-                       rec, depths, tiles, clamped, sort_keys, sort_vals, radii, wave_tiles, wave_kmin, wave_kmax, zero, zero2);
+                       rec, depths, tiles, clamped, sort_keys, sort_vals, radii, wave_tiles, wave_kmin, wave_kmax, zero, zero2,
+                       a.antialiasing);
     GS_LAUNCH_CHECK("preprocess", a.debug, s);
     return GS_OK;
 }

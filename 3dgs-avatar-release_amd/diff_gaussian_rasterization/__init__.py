@@ -5,7 +5,8 @@ GaussianRasterizationSettings, GaussianRasterizer`).
 Same public surface as the upstream package of the API generation the reference's call sites pin
 (12-field settings tuple ending in `prefiltered, debug`; `(color, radii)` return;
 gaussian_renderer/__init__.py:85-98,121-129): `GaussianRasterizationSettings`, `GaussianRasterizer`
-(with `markVisible`), `rasterize_gaussians`.  The bodies call the hand-written HIP library through
+(with `markVisible`), `rasterize_gaussians`.  The settings tuple also takes upstream's later 13th field,
+`antialiasing` (default False).  The bodies call the hand-written HIP library through
 the C ABI of include/gsplat_mi355.h; there is no CPU or PyTorch fallback.
 """
 import ctypes
@@ -35,6 +36,9 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+    # upstream's 13th field (GsFwdArgs.antialiasing): each Gaussian's opacity is scaled by how much the 0.3 px^2 screen-space
+    # dilation inflated its footprint.  Defaulted: the reference's 12-field construction is unchanged
+    antialiasing: bool = False
 
 
 _tls = threading.local()
@@ -93,6 +97,8 @@ class _GeomCache(object):
         tensors = (means3D, opacities, scales, rotations, cov3D, settings.viewmatrix, settings.projmatrix, settings.campos)
         return dict(scalars=(int(settings.image_height), int(settings.image_width), float(settings.tanfovx),
                              float(settings.tanfovy), float(settings.scale_modifier), int(means3D.shape[0]), _TILE_RECT,
+                             # the records hold the EFFECTIVE opacities: never shared across the flag, either way
+                             bool(getattr(settings, "antialiasing", False)),
                              # the cached state is only valid in stream order: a hit must come from the same stream
                              _lib.stream_handle(means3D.device) if stream_handle is None
                              else int(stream_handle),
@@ -256,6 +262,7 @@ def _make_args(settings, means3D, sh, colors_precomp, opacities, scales, rotatio
     a.prefiltered = int(bool(settings.prefiltered))
     a.debug = int(bool(settings.debug))
     a.tile_rect = _TILE_RECT
+    a.antialiasing = int(bool(getattr(settings, "antialiasing", False)))  # (a 12-field tuple of another package: off)
     st = _stats_words((dev.index, a.W, a.H))  # (not keyed by P: densification changes it every few hundred steps)
     if long_lists is None:  # a forward: decided from the previous frame of this shape (stale or missing words: a guess as good)
         long_lists = 1 if (_LONG_LISTS == "1" or (_LONG_LISTS == "auto" and int(st[0]) > 0)) else 0

@@ -110,7 +110,7 @@ def frame_stats(cam, cloud, pipe, bg):
         image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
         tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
         projmatrix=cam.full_proj_transform, sh_degree=cloud.sh_degree, campos=cam.camera_center, prefiltered=False,
-        debug=False)
+        debug=False, antialiasing=bool(getattr(pipe, "antialiasing", False)))  # (fewer pairs with it: smaller snug boxes)
     with torch.no_grad():
         st = forward_state(settings, cloud.xyz.detach(), cloud.opacity.detach(), shs=cloud.shs.detach(),
                            scales=cloud.scales.detach(), rotations=cloud.rotations.detach())

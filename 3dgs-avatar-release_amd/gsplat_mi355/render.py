@@ -19,10 +19,14 @@ _DEBUG = __import__("os").environ.get("GSPLAT_DEBUG", "0") == "1"
 class Pipe(object):
     """pipeline.* keys the renderer reads (configs/config.yaml:89-92)."""
 
-    def __init__(self, compute_cov3D_python=False, convert_SHs_python=False, debug=False, fuse_opacity=False):
+    def __init__(self, compute_cov3D_python=False, convert_SHs_python=False, debug=False, fuse_opacity=False,
+                 antialiasing=False):
         self.compute_cov3D_python = compute_cov3D_python
         self.convert_SHs_python = convert_SHs_python
         self.debug = debug
+        # not a reference key (upstream's later `pipe.antialiasing`): the rasterizer's `antialiasing` setting, for both
+        # rasterizer calls of a render() -- the opacity pass must see the colour pass's effective opacities
+        self.antialiasing = antialiasing
         # not a reference key: render the opacity image inside the colour pass (one rasterizer call with
         # with_opacity=True) instead of the reference's second call with colours = 1
         self.fuse_opacity = fuse_opacity
@@ -90,7 +94,7 @@ def render(data, pc, pipe, bg_color, scaling_modifier=1.0, colors_precomp=None, 
         image_height=int(data.image_height), image_width=int(data.image_width), tanfovx=tanfovx, tanfovy=tanfovy,
         bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=data.world_view_transform,
         projmatrix=data.full_proj_transform, sh_degree=pc.sh_degree, campos=data.camera_center, prefiltered=False,
-        debug=pipe.debug)
+        debug=pipe.debug, antialiasing=bool(getattr(pipe, "antialiasing", False)))
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     means3D = xyz
     means2D = screenspace_points

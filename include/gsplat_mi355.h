@@ -58,7 +58,7 @@ extern "C" {
  * -- all of them with a->debug == 0 and the stage timer (gs_profile_enable) off.  Not capture-safe: gs_forward (it waits
  * for the pair count on the host), gs_adam_step (the step number is a host scalar: a replay would repeat the captured
  * step's bias correction; gs_adam_step_ex likewise for a tensor without a device step), knn_dist2 / knn_points (their sorts clear tables with memset nodes: untested under replay),
- * anything in debug mode. */
+ * anything in debug mode.  GsFwdArgs.antialiasing changes nothing about capture safety: it is a kernel argument of launches that are there either way. */
 
 /* Arguments of one rasterizer call: the fields of GaussianRasterizationSettings
  * (gaussian_renderer/__init__.py:85-98) plus the tensors of GaussianRasterizer.forward
@@ -115,6 +115,18 @@ typedef struct GsFwdArgs {
     int32_t forward_only; /* !=0: no backward will follow this forward (a frame rendered under no_grad): the render launch does
                            * not prepare the backward's row marks on the side (55 MB of streaming stores at config 3).  A
                            * backward that is run on the state anyway prepares them itself, as after a first backward */
+    int32_t antialiasing; /* upstream's `antialiasing` setting (the Mip-Splatting compensation).  Let (a0, b, c0) be the
+                           * EWA-projected 2-D covariance before the 0.3 px^2 screen-space dilation, a = a0 + 0.3, c = c0 + 0.3,
+                           * det0 = a0 c0 - b^2, det1 = a c - b^2, s = sqrt(max(0.000025, det0 / det1)).  !=0: the opacity
+                           * everything downstream of the projection sees is o' = o s (the tile_rect = 1 box, the splat record
+                           * and through it the render loops, the 1 - T opacity image and gs_forward_shared); radii, conic,
+                           * depth, colour, the 3-sigma square and culling do not depend on it.  0: o' = o.  Every gs_backward*
+                           * of such a forward (the SAME value must be passed) returns dL/do = s dL/do' and, where
+                           * det0 / det1 > 0.000025, adds dL/do' o' (1/2) (c0/det0 - c/det1), dL/do' o' (1/2) (a0/det0 - a/det1)
+                           * and dL/do' o' b (1/det1 - 1/det0) to dL/da, dL/dc and dL/db (b the one off-diagonal parameter) in
+                           * front of the chain to cov3D (scales, rotations) and means3D; where the clamp is active (det0 <= 0
+                           * included) nothing is added and dL/do = 0.005 dL/do'.  Takes the place of tail padding: no
+                           * offset and no state-buffer layout changes */
 } GsFwdArgs;
 
 /* The eight gradient outputs of upstream `rasterize_gaussians_backward`, in the order the
@@ -178,7 +190,9 @@ int gs_forward(const GsFwdArgs* a, void* geom, size_t geom_bytes, void* binning,
  * a fresh geom / image state (usable by gs_backward) and shares the binning state.  The image is composited from the
  * quadrant lists the first render recorded (same bits as a stand-alone render); if colors_precomp is all ones -- found
  * out on the device, one word of geom_src is written -- it is instead written as 1 - T of the first render (+ T bg),
- * equal to the composited image to fp32 rounding.  Pass the SAME a->long_lists as to the first render.  Its gradients
+ * equal to the composited image to fp32 rounding.  Pass the SAME a->long_lists as to the first render, and the SAME
+ * a->antialiasing: the records are copied, so this render has the first render's effective opacities whatever it is told,
+ * and its backward must scale them the same way.  Its gradients
  * can be had together with the first render's in one pass: gs_backward_with_second. */
 int gs_forward_shared(const GsFwdArgs* a, const void* geom_src, const void* img_src, void* geom, size_t geom_bytes,
                       void* binning, size_t binning_bytes, void* img, size_t img_bytes, int64_t num_rendered,
