@@ -37,7 +37,8 @@ STRICT = {"preprocess.hip", "knn.hip", "densify.hip", "aiap.hip", "hashgrid.hip"
 NO_SLP = {"render_fwd.hip", "render_bwd.hip"}
 SOURCES = ["capi.hip", "preprocess.hip", "radix_sort.hip", "depth_sort.hip", "binning.hip", "render_fwd.hip", "render_bwd.hip",
            "gaussian_bwd.hip", "knn.hip", "loss.hip", "prepass.hip", "optim.hip", "densify.hip", "aiap.hip", "hashgrid.hip",
-           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip", "debug_stats.hip"]
+           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip", "debug_stats.hip",
+           "second_colors.hip"]
 
 
 def hipcc():

@@ -580,9 +580,19 @@ static int backward_impl(const GsFwdArgs* a, const int32_t* radii, const void* g
         rc = sync_if_debug(a, "render_backward", s);
         if (rc != GS_OK) return rc;
     }
-    StageScope sc_("gaussian_bwd", s);
-    return launch_gaussian_backward(*a, radii, g.rec, g.tiles, g.clamped, reinterpret_cast<const uint32_t*>(b.marks),
-                                    (const float*)scratch, sums, b.marks_flag, *gr, s);
+    { StageScope sc_("gaussian_bwd", s);
+    rc = launch_gaussian_backward(*a, radii, g.rec, g.tiles, g.clamped, reinterpret_cast<const uint32_t*>(b.marks),
+                                  (const float*)scratch, sums, b.marks_flag, *gr, s); }
+    if (rc != GS_OK || !second || !second->dL_dcolors) return rc;
+    // the second image's own colour gradient (second_colors.hip): a forward-shaped walk of the tile lists, its per-pair rows
+    // in the rows region of the scratch, which the per-Gaussian backward enqueued above was the last to read
+    { StageScope sc_("second_colors", s);
+    rc = launch_second_colors(g.rec, g.tiles, radii, b.point_list, im.ranges, im.order, im.n_contrib, second->dL_dpix, a->P, a->W,
+                              a->H, D, PairCount{g.count + COUNT_PAIRS, (uint32_t)D}, few_long_lists_mode(im.ntiles, a->long_lists),
+                              scratch, scratch_rows_bytes(D),
+                              second->dL_dcolors, a->debug, s); }
+    if (rc != GS_OK) return rc;
+    return sync_if_debug(a, "second_colors", s);
 }
 
 int gs_backward(const GsFwdArgs* a, const int32_t* radii, const void* geom, size_t geom_bytes, void* binning,

@@ -417,13 +417,16 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 __device__ __forceinline__ uint32_t wave_min(uint32_t x) { return ~wave_max(~x); }
-// (float: the sum is taken in the ladder's fixed order -- the same bits on every run)
-__device__ __forceinline__ float wave_sum(float x) {
+// (float: the sum is taken in the ladder's fixed order -- the same bits on every run; lane 63 of the scan holds it)
+__device__ __forceinline__ float wave_scan_incl(float x) {
 #define GS_FSUM_STEP(CTRL, MASK) x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, MASK, 0xF, false));
     GS_FSUM_STEP(0x111, 0xF) GS_FSUM_STEP(0x112, 0xF) GS_FSUM_STEP(0x114, 0xF) GS_FSUM_STEP(0x118, 0xF)
     GS_FSUM_STEP(0x142, 0xA) GS_FSUM_STEP(0x143, 0xC)
 #undef GS_FSUM_STEP
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+    return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_scan_incl(x)), 63));
 }
 
 // ---- rank segments (binning.hip).  The ranking is cut into `nseg` SEGMENTS of about equal work, not of equal length: the
@@ -741,6 +744,16 @@ static inline size_t scratch_sums_bytes(int P) { return align_up((size_t)(P > 0 
 static inline size_t scratch_total_bytes(int64_t D, int P, int ntiles) {
     return scratch_rows_bytes(D) + scratch_sums_bytes(P) + align_up((size_t)ntiles * 4, 256);  // (the row marks: BinLayout)
 }
+
+// second_colors.hip: dL_dcolors[P,3] of a second image of the same geometry = sum over pixels of alpha T dL_dpix2, through one
+// 16-byte row per pair in `workspace` (the rows region of the backward scratch, free once the per-Gaussian backward is
+// enqueued; behind the rows, where the lists are few and long, the per-chunk transmittance products)
+// (`pc`: the frame's pair count on the device against the capacity D -- a frame that did not fit has empty lists, no row
+// written, and gets zeros)
+int launch_second_colors(const float* rec, const uint32_t* tiles, const int32_t* radii, const uint32_t* point_list,
+                         const uint32_t* ranges, const uint32_t* order, const uint32_t* n_contrib, const float* dL_dpix2, int P,
+                         int W, int H, int64_t D, PairCount pc, bool few_long_lists, void* workspace, size_t workspace_bytes, float* dL_dcolors,
+                         int debug, hipStream_t s);
 
 // report counters (debug_stats.hip): out[0] = pairs composited (alpha >= 1/255 before the pixel is done), out[1] = sum of n_contrib
 int launch_pair_stats(const float* rec, const uint32_t* point_list, const uint32_t* ranges, const uint32_t* n_contrib, int W, int H,

@@ -5,12 +5,14 @@ GaussianRasterizationSettings, GaussianRasterizer`).
 Same public surface as the upstream package of the API generation the reference's call sites pin
 (12-field settings tuple ending in `prefiltered, debug`; `(color, radii)` return;
 gaussian_renderer/__init__.py:85-98,121-129): `GaussianRasterizationSettings`, `GaussianRasterizer`
-(with `markVisible`), `rasterize_gaussians`.  The settings tuple also takes upstream's later 13th field,
+(with `markVisible`), `rasterize_gaussians`.  `forward(..., with_invdepth=True)` gives upstream's later
+`(color, radii, invdepths)`.  The settings tuple also takes upstream's later 13th field,
 `antialiasing` (default False).  The bodies call the hand-written HIP library through
 the C ABI of include/gsplat_mi355.h; there is no CPU or PyTorch fallback.
 """
 import ctypes
 import os
+import sys
 import threading
 import weakref
 from typing import NamedTuple
@@ -283,30 +285,37 @@ def _dump_snapshot(path, raster_settings, tensors):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, with_opacity=False, l1_target=None):
+                        raster_settings, with_opacity=False, l1_target=None, with_invdepth=False):
     """(color, radii), as upstream.  with_opacity=True (an extension; see GaussianRasterizer.forward) adds the
     opacity render as a third result, computed and differentiated inside the same pass; l1_target (an extension, too)
     adds mean |color - l1_target| as the last result, computed by the render launch and differentiated in the
-    backward's own pixel prologue."""
+    backward's own pixel prologue.  with_invdepth=True adds upstream's inverse-depth image (1, H, W) behind them:
+    (color, radii[, opacity][, invdepth][, l1])."""
+    if with_invdepth and with_opacity:
+        # the C backward takes either the opacity channel or a second image along, not both
+        raise NotImplementedError("diff_gaussian_rasterization: with_invdepth and with_opacity cannot be combined in one "
+                                  "call (render the opacity image with a second call on the same geometry)")
     if l1_target is not None:
         l1_target = _f32c(l1_target, "l1_target")
         if tuple(l1_target.shape) != (3, int(raster_settings.image_height), int(raster_settings.image_width)):
             raise ValueError("diff_gaussian_rasterization: l1_target must be a (3, H, W) image")
     dep = None
-    if (_FUSE_SECOND and _SHARE and not with_opacity and torch.is_grad_enabled() and colors_precomp is not None
+    if (_FUSE_SECOND and _SHARE and not with_opacity and not with_invdepth and torch.is_grad_enabled() and colors_precomp is not None
             and colors_precomp.numel() and not colors_precomp.requires_grad and (sh is None or sh.numel() == 0)):
         dep = _second_render_dependency(means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
     if not torch.is_grad_enabled():
         # no_grad (the reference's render loop, render.py:51-62): no autograd node would be built, and Function.apply
         # costs ~10 us of Python per call for building none -- a tenth of a forward-only frame at 50k Gaussians
-        color, radii, opacity, l1 = _RasterizeGaussians.forward(_InferenceCtx(), means3D, means2D, sh, colors_precomp, opacities,
-                                                                scales, rotations, cov3Ds_precomp, raster_settings,
-                                                                bool(with_opacity), None, l1_target)
+        color, radii, opacity, l1, invdepth = _RasterizeGaussians.forward(
+            _InferenceCtx(), means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+            raster_settings, bool(with_opacity), None, l1_target, bool(with_invdepth))
     else:
-        color, radii, opacity, l1 = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales,
-                                                               rotations, cov3Ds_precomp, raster_settings, bool(with_opacity),
-                                                               dep, l1_target)
+        color, radii, opacity, l1, invdepth = _RasterizeGaussians.apply(
+            means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+            bool(with_opacity), dep, l1_target, bool(with_invdepth))
     out = (color, radii, opacity) if with_opacity else (color, radii)
+    if with_invdepth:
+        out = out + (invdepth,)
     return out + (l1,) if l1_target is not None else out
 
 
@@ -343,7 +352,7 @@ def _second_render_dependency(means3D, means2D, opacities, scales, rotations, co
 
 class _InferenceCtx(object):
     """What _forward / _finish touch of an autograd context, for a call under no_grad: nothing is saved, no node exists."""
-    needs_input_grad = (False,) * 12
+    needs_input_grad = (False,) * 13
 
     def set_materialize_grads(self, value):
         pass
@@ -358,15 +367,15 @@ class _InferenceCtx(object):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, with_opacity=False, dep=None, l1_target=None):
+                raster_settings, with_opacity=False, dep=None, l1_target=None, with_invdepth=False):
         if not raster_settings.debug:
             return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                                cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target)
+                                                cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target, with_invdepth)
         # upstream's debug mode: the arguments are kept aside and written to snapshot_fw.dump if the native call fails
         args = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         try:
             return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                                cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target)
+                                                cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target, with_invdepth)
         except Exception:
             _dump_snapshot("snapshot_fw.dump", raster_settings, args)
             print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
@@ -374,8 +383,9 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                 raster_settings, with_opacity=False, dep=None, l1_target=None):
+                 raster_settings, with_opacity=False, dep=None, l1_target=None, with_invdepth=False):
         ctx.with_opacity = bool(with_opacity)
+        ctx.with_invdepth = bool(with_invdepth)
         ctx.l1_target = None
         l1 = None  # (never kept on ctx: an output held by its own node is a reference cycle around the whole saved state)
         ctx.defer_to = None
@@ -424,8 +434,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             gkey = (_geom_cache.key(raster_settings, means3D, opacities, scales, rotations, cov3Ds_precomp, stream_h,
                                     capturing)
                     if share else None)
-            hit = _geom_cache.take(dev, gkey) if (share and l1_target is None) else None  # (a shared-geometry render has no fused loss)
-            if not share or l1_target is not None:
+            # (a shared-geometry render has no fused loss, and no depths of its own for the inverse-depth image)
+            hit = _geom_cache.take(dev, gkey) if (share and l1_target is None and not ctx.with_invdepth) else None
+            if not share or l1_target is not None or ctx.with_invdepth:
                 _geom_cache.offer.pop(dev.index, None)
             ctx.geom_entry = None
             if hit is not None:
@@ -489,7 +500,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                     ctx.geom_entry = _GeomEntry(gkey, geom, binning, img, num_rendered, capacity, radii)
                     ctx.geom_entry.color_ref = weakref.ref(color)
                     ctx.geom_entry.means2D_id = id(means2D_in)
-                    ctx.geom_entry.allow_second = not ctx.with_opacity
+                    ctx.geom_entry.allow_second = not ctx.with_opacity and not ctx.with_invdepth
                     ctx.geom_entry.long_lists = int(a.long_lists)
                     _geom_cache.put(dev, ctx.geom_entry)
                 return _RasterizeGaussians._finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp,
@@ -525,7 +536,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 ctx.geom_entry = _GeomEntry(gkey, geom, binning, img, num_rendered, capacity, radii)
                 ctx.geom_entry.color_ref = weakref.ref(color)  # (the tensor this call returns: autograd tracks it)
                 ctx.geom_entry.means2D_id = id(means2D_in)
-                ctx.geom_entry.allow_second = not ctx.with_opacity
+                ctx.geom_entry.allow_second = not ctx.with_opacity and not ctx.with_invdepth
                 ctx.geom_entry.long_lists = int(a.long_lists)
                 _geom_cache.put(dev, ctx.geom_entry)
             return _RasterizeGaussians._finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp,
@@ -542,6 +553,40 @@ class _RasterizeGaussians(torch.autograd.Function):
             H, W = int(raster_settings.image_height), int(raster_settings.image_width)
             opacity = torch.empty(1, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.gs_opacity_image(ctypes.byref(a), img.data_ptr(), img.numel(), opacity.data_ptr(), sptr))
+        invdepth = None
+        second = ()
+        if ctx.with_invdepth:
+            # upstream's inverse-depth image, sum alpha T / z: a second render of THIS call's geometry (recorded quadrant
+            # lists, same alpha and T) with the colours (1/z, 1/z, 1/z) over a zero background; z = the view-space depths
+            # the forward stored, 1/z = 0 for the Gaussians it culled.  The render's states stay with this node: its
+            # backward differentiates both images in one pass (gs_backward_with_second with dL_dcolors)
+            L = _lib.load()
+            H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+            P = int(means3D.shape[0])
+            fptr = ctypes.c_void_p()
+            _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_DEPTHS, ctypes.byref(fptr)))
+            off = int(fptr.value) - geom.data_ptr()
+            depths = geom[off:off + 4 * P].view(torch.float32)
+            invz = torch.where(radii > 0, 1.0 / depths, torch.zeros((), dtype=torch.float32, device=dev))
+            colors2 = invz.unsqueeze(1).expand(P, 3).contiguous()
+            bg2 = torch.zeros(3, dtype=torch.float32, device=dev)
+            a2 = _lib.GsFwdArgs.from_buffer_copy(a)
+            a2.shs, a2.M, a2.colors_precomp, a2.bg = None, 0, colors2.data_ptr(), bg2.data_ptr()
+            a2.frame_stats = a2.l1_target = a2.l1_loss = a2.l1_grad = None
+            geom2 = torch.empty_like(geom)  # (what gs_forward_shared recolours into; nothing reads it afterwards: DESIGN.md 5b)
+            img2 = torch.empty_like(img)
+            color2 = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.gs_forward_shared(ctypes.byref(a2), geom.data_ptr(), img.data_ptr(), geom2.data_ptr(), geom2.numel(),
+                                           _lib.ptr(binning), binning.numel() if binning is not None else 0,
+                                           img2.data_ptr(), img2.numel(), capacity, color2.data_ptr(), sptr))
+            # the recolouring launch has set this geometry's "a second render's colours are not all ones" word; cleared
+            # again, so that a following call's shared render (the reference's opacity pass) finds what it would have
+            # found without the flag
+            _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_COUNT, ctypes.byref(fptr)))
+            off = int(fptr.value) - geom.data_ptr() + 8 * _lib.GS_COUNT_NOT_ONES
+            geom[off:off + 8].zero_()
+            invdepth = color2[:1]
+            second = (colors2, color2, img2)  # (geom2 holds nothing the backward reads)
         ctx.raster_settings = raster_settings
         ctx.long_lists = int(a.long_lists)  # the backward must be told the same (GsFwdArgs.long_lists)
         ctx.fwd_args = (a, keep)  # the argument block (pointers into the saved tensors) serves the backward as it is
@@ -552,23 +597,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(means3D, sh if sh is not None else empty,
                               colors_precomp if colors_precomp is not None else empty, opacities,
                               scales if scales is not None else empty, rotations if rotations is not None else empty,
-                              cov3Ds_precomp if cov3Ds_precomp is not None else empty, radii, geom, binning, img, color)
+                              cov3Ds_precomp if cov3Ds_precomp is not None else empty, radii, geom, binning, img, color,
+                              *second)
         ctx.mark_non_differentiable(radii)
-        return color, radii, opacity, l1
+        return color, radii, opacity, l1, invdepth
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None, grad_invdepth=None):
         if not ctx.raster_settings.debug:
-            return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1)
+            return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1, grad_invdepth)
         try:
-            return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1)
+            return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1, grad_invdepth)
         except Exception:
             _dump_snapshot("snapshot_bw.dump", ctx.raster_settings, tuple(ctx.saved_tensors[:8]) + (grad_out_color,))
             print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
             raise
 
     @staticmethod
-    def _backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None):
+    def _backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None, grad_invdepth=None):
         L = _lib.load()
         tgt = getattr(ctx, "defer_to", None)
         if tgt is not None and tgt.geom is not None and grad_out_color is not None:
@@ -577,7 +623,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             saved = ctx.saved_tensors
             tgt.second = dict(colors=saved[2], out_color=saved[11], grad=_f32c(grad_out_color, "grad_out_color"), img=saved[10],
                               long_lists=ctx.long_lists)
-            return (None,) * 12
+            return (None,) * 13
         entry = getattr(ctx, "geom_entry", None)
         second = None
         if entry is not None:  # a render after this backward (e.g. after an optimiser step) must not meet this state
@@ -585,7 +631,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             entry.release()
             ctx.geom_entry = None
         (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img,
-         color) = ctx.saved_tensors
+         color) = ctx.saved_tensors[:12]
         has_sh, has_col, has_sr, has_cov = ctx.present
         settings = ctx.raster_settings
         dev = means3D.device
@@ -593,7 +639,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         W, H = int(settings.image_width), int(settings.image_height)
         D = ctx.capacity
         use_l1 = ctx.l1_target is not None and grad_l1 is not None
-        if grad_out_color is None and not use_l1:  # only the opacity render was used downstream
+        # the inverse-depth image's gradient, if that image was used downstream (None: today's plain path, bit for bit)
+        g_inv = _f32c(grad_invdepth, "grad_invdepth") if (getattr(ctx, "with_invdepth", False) and grad_invdepth is not None) else None
+        if grad_out_color is None and not use_l1:  # only the opacity / inverse-depth render was used downstream
             grad_out_color = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
         g = _f32c(grad_out_color, "grad_out_color") if grad_out_color is not None else None
         g_l1 = _f32c(grad_l1, "grad_l1") if use_l1 else None
@@ -627,7 +675,28 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_rot = torch.empty(P, 4, **f) if has_sr else None
             gr = _lib.GsGrads(_lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_sh), _lib.ptr(d_colors),
                               _lib.ptr(d_opacity), _lib.ptr(d_scales), _lib.ptr(d_rot), _lib.ptr(d_cov3D))
-            if second is not None and g_op is None:
+            if g_inv is not None:
+                # both images in one pass: the second image is this node's own inverse-depth render, whose colours (1/z)
+                # DO depend on an input -- dL_dcolors of the second image is asked for, and the chain through z is closed
+                # here: d(1/z)/d(means3D) = -1/z^2 * viewmatrix[:3, 2]
+                colors2, color2, img2 = ctx.saved_tensors[12:15]
+                g2 = torch.zeros(3, H, W, **f)
+                g2[0].copy_(g_inv.reshape(H, W))
+                d_colors2 = torch.empty(P, 3, **f)
+                si = _lib.GsSecondImage(colors2.data_ptr(), color2.data_ptr(), g2.data_ptr(), img2.data_ptr(), img2.numel(),
+                                        ctx.long_lists, d_colors2.data_ptr())
+                _lib.check(L.gs_backward_with_second(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
+                                                     binning.data_ptr(), binning.numel(), img.data_ptr(), img.numel(), D,
+                                                     color.data_ptr(), gp, ctypes.byref(si), scratch.data_ptr(),
+                                                     scratch_bytes, ctypes.byref(gr), sptr))
+                # (tests: gsplat_mi355.debug.second_colors_hook, if that module is loaded)
+                hook = getattr(sys.modules.get("gsplat_mi355.debug"), "second_colors_hook", None)
+                if hook is not None:
+                    hook(d_colors2)
+                invz = colors2[:, 0]
+                view = _f32c(settings.viewmatrix.to(dev), "viewmatrix")
+                d_means3D.addcmul_((d_colors2.sum(1) * invz * invz).unsqueeze(1), view[:3, 2].unsqueeze(0), value=-1.0)
+            elif second is not None and g_op is None:
                 si = _lib.GsSecondImage(second["colors"].data_ptr(), second["out_color"].data_ptr(), second["grad"].data_ptr(),
                                         second["img"].data_ptr(), second["img"].numel(), int(second["long_lists"]))
                 _lib.check(L.gs_backward_with_second(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
@@ -646,7 +715,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                       color.data_ptr(), gp, g_op.data_ptr(), scratch.data_ptr(),
                                                       scratch_bytes, ctypes.byref(gr), sptr))
         return (d_means3D, d_means2D, d_sh, d_colors if has_col else None, d_opacity, d_scales, d_rot,
-                d_cov3D if has_cov else None, None, None, None, None)
+                d_cov3D if has_cov else None, None, None, None, None, None)
 
 
 class GaussianRasterizer(nn.Module):
@@ -670,14 +739,20 @@ class GaussianRasterizer(nn.Module):
         return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, with_opacity=False, l1_target=None):
+                cov3D_precomp=None, with_opacity=False, l1_target=None, with_invdepth=False):
         """Upstream signature and results: (color[3,H,W], radii[N]).  `with_opacity=True` is an extension: a third
         result, the opacity render [1,H,W] -- what the reference gets from a second call with colours = 1
         (gaussian_renderer/__init__.py:132-142, `[:1]`) -- produced and differentiated inside the same pass.
         `l1_target` (a (3,H,W) image) is an extension, too: a LAST result, the scalar mean |color - l1_target| -- the
         reference's `l1_loss(image, gt_image)` (train.py:121, utils/loss_utils.py:21-22) -- computed by the render launch
         from the colours it has just composited; its gradient w.r.t. the image is formed per pixel inside the backward
-        (added to whatever gradient `color` itself receives), so no gradient image is written or read for it."""
+        (added to whatever gradient `color` itself receives), so no gradient image is written or read for it.
+        `with_invdepth=True` adds upstream's inverse-depth image [1,H,W] -- sum alpha T / z_view over the Gaussians
+        composited at the pixel, no background term, 0 where nothing contributes -- so that the result is upstream's
+        current `(color, radii, invdepths)`; in general `(color, radii[, opacity][, invdepth][, l1])`.  It is rendered from
+        the geometry of the same call and differentiated in the same backward pass as the colour image (gradients reach
+        opacities, means2D, the covariance inputs and means3D, the latter also through z).  Not together with
+        `with_opacity` (NotImplementedError)."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -695,4 +770,5 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   raster_settings, with_opacity=with_opacity, l1_target=l1_target)
+                                   raster_settings, with_opacity=with_opacity, l1_target=l1_target,
+                                   with_invdepth=with_invdepth)

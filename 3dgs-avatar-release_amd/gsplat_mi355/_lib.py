@@ -26,7 +26,8 @@ class GsFwdArgs(ctypes.Structure):
 
 class GsSecondImage(ctypes.Structure):  # include/gsplat_mi355.h: GsSecondImage
     _fields_ = [("colors", c_void_p), ("out_color", c_void_p), ("dL_dpix", c_void_p), ("img", c_void_p),
-                ("img_bytes", c_size_t), ("long_lists", c_int32)]
+                ("img_bytes", c_size_t), ("long_lists", c_int32),
+                ("dL_dcolors", c_void_p)]  # (trailing, NULL by default: the six-field positional construction stays valid)
 
 
 class GsGrads(ctypes.Structure):
@@ -62,6 +63,9 @@ GS_ADAM_MAX_TENSORS = 16
 # `field` of gs_geom_field / gs_binning_field / gs_image_field (include/gsplat_mi355.h: GsGeomField, GsBinningField, GsImageField)
 GS_GEOM_DEPTHS, GS_GEOM_TILES, GS_GEOM_REC, GS_GEOM_CLAMPED, GS_GEOM_SORTED_IDX, GS_GEOM_COUNT, GS_GEOM_FIELDS = range(7)
 GS_BIN_POINT_LIST, GS_BIN_QLIST, GS_BIN_FIELDS = range(3)
+# u64 word of the block GS_GEOM_COUNT names that says "a second render's colours are not all ones" (csrc/common.h:
+# COUNT_NOT_ONES; tests/test_invdepth_host.py holds the two together)
+GS_COUNT_NOT_ONES = 2
 (GS_IMG_RANGES, GS_IMG_N_CONTRIB, GS_IMG_FINAL_T, GS_IMG_QCOUNT, GS_IMG_NCON_C, GS_IMG_ORDER, GS_IMG_CW_HDR, GS_IMG_CW_UNITS,
  GS_IMG_CW_FLAG, GS_IMG_CW_REC, GS_IMG_FIELDS) = range(11)
 

@@ -9,6 +9,11 @@ from gsplat_mi355 import _lib
 from diff_gaussian_rasterization import GaussianRasterizationSettings, _make_args, _f32c
 
 
+# a callable given dL_dcolors (P, 3) of the inverse-depth render -- the output of csrc/second_colors.hip -- by every backward
+# of diff_gaussian_rasterization that computes it (None: off)
+second_colors_hook = None
+
+
 def _view(owner, ptr, nbytes, dtype):
     """numpy copy of `nbytes` at device address `ptr`, which lies inside the uint8 tensor `owner`."""
     off = ptr - owner.data_ptr()

@@ -20,7 +20,7 @@ class Pipe(object):
     """pipeline.* keys the renderer reads (configs/config.yaml:89-92)."""
 
     def __init__(self, compute_cov3D_python=False, convert_SHs_python=False, debug=False, fuse_opacity=False,
-                 antialiasing=False):
+                 antialiasing=False, invdepth=False):
         self.compute_cov3D_python = compute_cov3D_python
         self.convert_SHs_python = convert_SHs_python
         self.debug = debug
@@ -30,6 +30,10 @@ class Pipe(object):
         # not a reference key: render the opacity image inside the colour pass (one rasterizer call with
         # with_opacity=True) instead of the reference's second call with colours = 1
         self.fuse_opacity = fuse_opacity
+        # not a reference key: also render upstream's inverse-depth image (the rasterizer's with_invdepth=True); the
+        # package carries it as `invdepth_render`.  The C backward takes one extra image along, so with fuse_opacity
+        # set as well the opacity image comes from the reference's second call
+        self.invdepth = invdepth
 
 
 class RenderPackage(object):
@@ -112,8 +116,14 @@ def render(data, pc, pipe, bg_color, scaling_modifier=1.0, colors_precomp=None, 
                                 fwd_transform=getattr(pc, "fwd_transform", None))
     shs = None if colors_precomp is not None else pc.shs
     opacity_image = None
+    invdepth_image = None
     l1 = None
-    if return_opacity and getattr(pipe, "fuse_opacity", False):
+    if getattr(pipe, "invdepth", False):
+        res = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, l1_target=l1_target,
+                         with_invdepth=True)
+        rendered_image, radii, invdepth_image = res[:3]
+    elif return_opacity and getattr(pipe, "fuse_opacity", False):
         res = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
                          scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, with_opacity=True,
                          l1_target=l1_target)
@@ -131,7 +141,7 @@ def render(data, pc, pipe, bg_color, scaling_modifier=1.0, colors_precomp=None, 
                                       cov3D_precomp=cov3D_precomp)
         opacity_image = opacity_image[:1]
     return RenderPackage(deformed_gaussian=pc, render=rendered_image, viewspace_points=screenspace_points,
-                         radii=radii, opacity_render=opacity_image, l1=l1)
+                         radii=radii, opacity_render=opacity_image, l1=l1, invdepth_render=invdepth_image)
 
 
 class _L1Loss(torch.autograd.Function):

@@ -46,6 +46,7 @@ extern "C" {
  *   gs_forward_render      with a->frame_stats == NULL, at a fixed capacity (a frame whose count exceeds it renders
  *                          empty: read the count afterwards, outside the graph)
  *   gs_forward_shared (P > 0), gs_opacity_image, gs_backward, gs_backward_with_opacity, gs_backward_with_second,
+ *   (with GsSecondImage.dL_dcolors, too: kernel launches only),
  *   gs_mark_visible, gs_l1_loss, gs_bce_loss, gs_ssim_*, gs_build_covariance*, gs_sh2rgb* (view_noise_host == NULL),
  *   gs_densify_stats, gs_densify_plan (count_host_pinned == NULL), gs_densify_apply, gs_reset_opacity,
  *   gs_aiap_forward, gs_aiap_backward, gs_hashgrid_forward, gs_hashgrid_backward, gs_skin_weights_forward,
@@ -229,11 +230,16 @@ int gs_backward_with_opacity(const GsFwdArgs* a, const int32_t* radii, const voi
 /* A SECOND image rendered from the same geometry with other colours (gs_forward_shared: the reference's opacity pass,
  * gaussian_renderer/__init__.py:132-142) differentiated in the same pass as the first: alpha and T are shared, so the
  * second image adds one dot product per (pixel, Gaussian) step and one term to Gtot instead of a whole second backward.
- * The gradients are the SUM of both images' gradients w.r.t. the shared inputs; the second image's colours get none
- * (they must be constants); dL_dcolors / dL_dsh are the first image's.  `img` = the image state gs_forward_shared
- * filled for the second render (its checkpoints; a word of it says whether that render's colours were all (1, 1, 1), in
- * which case the pass needs no second colours at all: the reference's case), `long_lists` the value that render was
- * given. */
+ * The gradients are the SUM of both images' gradients w.r.t. the shared inputs; dL_dcolors / dL_dsh of `grads` are the
+ * first image's, and the second image's colours get theirs when asked (GsSecondImage.dL_dcolors).  `img` = the image
+ * state gs_forward_shared filled for the second render (its checkpoints; a word of it says whether that render's colours
+ * were all (1, 1, 1), in which case the pass needs no second colours at all: the reference's case), `long_lists` the
+ * value that render was given.
+ * GsSecondImage.dL_dcolors, when not NULL, adds two launches behind the per-Gaussian backward (three where the tile lists
+ * are few and long): a walk of the tile lists that writes one row of sum alpha T dL_dpix per pair into the rows region of
+ * `scratch`, free by then, and a per-Gaussian sum of the rows.  No atomics: the same bits on every run.  A frame whose
+ * pair count exceeds `D` (it rendered empty) gets zeros.  NULL: the call is what it was without the field, launch for
+ * launch. */
 typedef struct GsSecondImage {
     const float* colors;    /* [P,3] colors_precomp of the second render */
     const float* out_color; /* [3,H,W] its result */
@@ -241,6 +247,7 @@ typedef struct GsSecondImage {
     const void* img;        /* its image state */
     size_t img_bytes;
     int32_t long_lists;
+    float* dL_dcolors;      /* [P,3] or NULL: the gradient of `colors`, every row written (zeros for culled Gaussians) */
 } GsSecondImage;
 int gs_backward_with_second(const GsFwdArgs* a, const int32_t* radii, const void* geom, size_t geom_bytes,
                             void* binning, size_t binning_bytes, const void* img, size_t img_bytes, int64_t D,
