@@ -38,10 +38,18 @@ def _sh_rgb(deg, sh, dirs):
 
 def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, means2D, opacities,
            shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=0,
-           scale_modifier=1.0):
+           scale_modifier=1.0, antialiasing=False):
     """All tensor arguments float64.  `means2D` (N,3) is the zero 'screenspace_points' tensor of
     gaussian_renderer/__init__.py:76: its gradient is defined as dL/d(NDC position of the centre),
-    which is what the reference wrapper returns for it.  Returns (color[3,H,W], radii[N], aux)."""
+    which is what the reference wrapper returns for it.  Returns (color[3,H,W], radii[N], aux).
+
+    `antialiasing` (GsFwdArgs.antialiasing, include/gsplat_mi355.h): alpha uses o' = o s with
+    s = sqrt(max(0.000025, det0 / det1)), det0 the determinant of the projected 2-D covariance before the 0.3
+    dilation and det1 after it; where the clamp is active s = 0.005 is a constant (no gradient through it).
+
+    aux also carries the images the rasterizer's options add, differentiable like the colour image:
+    `invdepth` (1,H,W) = sum_i w_i / depth_i over the included pairs (no background term) and `opacity`
+    (1,H,W) = (1 - T_final) + T_final bg[0]; and per Gaussian `s` (ones without the option) and `o_eff` = o s."""
     dt = torch.float64
     N = means3D.shape[0]
     V = viewmatrix.to(dt).reshape(4, 4)
@@ -87,6 +95,14 @@ def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, 
     b = cov[:, 0, 1]
     c = cov[:, 1, 1] + 0.3
     det = a * c - b * b
+    o_eff = opacities.reshape(-1)
+    if antialiasing:
+        ratio = (cov[:, 0, 0] * cov[:, 1, 1] - b * b) / det
+        free = ratio.detach() > 0.000025
+        s_aa = torch.where(free, torch.sqrt(torch.where(free, ratio, torch.ones_like(ratio))), torch.full_like(ratio, 0.005))
+        o_eff = o_eff * s_aa
+    else:
+        s_aa = torch.ones_like(det)
     conA, conB, conC = c / det, -b / det, a / det
     mid = 0.5 * (a + c)
     lam = mid + torch.sqrt(torch.clamp_min(mid * mid - det, 0.1))
@@ -121,7 +137,7 @@ def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, 
     dx = bx[o][None, :] - pixx[:, None]
     dy = by[o][None, :] - pixy[:, None]
     power = -0.5 * (conA[o][None] * dx * dx + conC[o][None] * dy * dy) - conB[o][None] * dx * dy
-    alpha = torch.clamp_max(opacities.reshape(-1)[o][None] * torch.exp(power), 0.99)
+    alpha = torch.clamp_max(o_eff[o][None] * torch.exp(power), 0.99)
     in_rect = ((tilex[:, None] >= minx[o][None]) & (tilex[:, None] < maxx[o][None]) &
                (tiley[:, None] >= miny[o][None]) & (tiley[:, None] < maxy[o][None]))
     valid = in_rect & (power.detach() <= 0) & (alpha.detach() >= 1.0 / 255.0)
@@ -141,5 +157,7 @@ def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, 
     color = Cpix + T_final[:, None] * bg.to(dt)[None]
     aux = dict(depth=depth, px=px, py=py, conic=torch.stack([conA, conB, conC], 1), rgb=rgb,
                T_final=T_final.view(H, W), include=include, order=order,
-               rect=torch.stack([minx, miny, maxx, maxy], 1))
+               rect=torch.stack([minx, miny, maxx, maxy], 1), s=s_aa, o_eff=o_eff,
+               invdepth=(w @ (1.0 / depth[o])).view(1, H, W),
+               opacity=((1.0 - T_final) + T_final * bg.to(dt)[0]).view(1, H, W))
     return color.t().reshape(3, H, W), radii, aux

@@ -36,14 +36,16 @@ def cov6_from_scale_rot(sv, q):
     return torch.stack([dot(0, 0), dot(0, 1), dot(0, 2), dot(1, 1), dot(1, 2), dot(2, 2)], 1)
 
 
-def project(means, c6, view, W, H, tanfovx, tanfovy):
-    """(a0, b, c0): the EWA-projected 2-D covariance BEFORE the dilation (gs_math.h cov2d, operation for operation)."""
+def project(means, c6, view, W, H, tanfovx, tanfovy, scalar=np.float32):
+    """(a0, b, c0): the EWA-projected 2-D covariance BEFORE the dilation (gs_math.h cov2d, operation for operation).
+    `scalar`: the type the focal lengths and clamp limits are formed in (the kernel's: fp32; np.float64 for a comparison
+    with oracle/dense_ref.py, which forms them in float64)."""
     dt = means.dtype
     V = view.to(dt)
-    f32 = lambda v: float(np.float32(v))  # the kernel's scalars are fp32 values
-    fx = f32(np.float32(W) / (np.float32(2.0) * np.float32(tanfovx)))
-    fy = f32(np.float32(H) / (np.float32(2.0) * np.float32(tanfovy)))
-    limx, limy = f32(np.float32(1.3) * np.float32(tanfovx)), f32(np.float32(1.3) * np.float32(tanfovy))
+    f32 = lambda v: float(scalar(v))  # the kernel's scalars are fp32 values
+    fx = f32(scalar(W) / (scalar(2.0) * scalar(tanfovx)))
+    fy = f32(scalar(H) / (scalar(2.0) * scalar(tanfovy)))
+    limx, limy = f32(scalar(1.3) * scalar(tanfovx)), f32(scalar(1.3) * scalar(tanfovy))
     px, py, pz = means[:, 0], means[:, 1], means[:, 2]
     tx = V[0, 0] * px + V[1, 0] * py + V[2, 0] * pz + V[3, 0]
     ty = V[0, 1] * px + V[1, 1] * py + V[2, 1] * pz + V[3, 1]
@@ -97,14 +99,14 @@ class Scene(object):
     """The rows `rows` (those the device reports visible) of a cloud, as leaves of the given dtype."""
 
     def __init__(self, means, opacity, view, W, H, tanfovx, tanfovy, cov6=None, scales=None, rotations=None,
-                 scale_modifier=1.0, rows=None, dtype=torch.float64):
+                 scale_modifier=1.0, rows=None, dtype=torch.float64, scalar=np.float32):
         n = np.asarray(means).shape[0]
         self.n, self.dtype = n, dtype
         self.rows = np.arange(n) if rows is None else np.flatnonzero(np.asarray(rows))
         pick = lambda x: _t(np.asarray(x, np.float32).reshape(n, -1)[self.rows], dtype)
         self.means = pick(means).requires_grad_(True)
         self.opacity = pick(opacity)[:, 0]
-        self.cam = (_t(view, dtype).reshape(4, 4), int(W), int(H), float(tanfovx), float(tanfovy))
+        self.cam = (_t(view, dtype).reshape(4, 4), int(W), int(H), float(tanfovx), float(tanfovy), scalar)
         if cov6 is not None:
             self.cov6, self.sv, self.rot = pick(cov6).requires_grad_(True), None, None
         else:

@@ -207,3 +207,40 @@ def covariance6_cpu(cloud, scale_modifier=1.0):
     L = R * (scale_modifier * cloud.scales).unsqueeze(1)
     S = L @ L.transpose(1, 2)
     return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], dim=1).contiguous()
+
+
+NEAR = 1e-4  # relative distance from a threshold decision within which a float64 reference calls a pair undecided
+
+
+def undecided_pairs(aux, W, H):
+    """Given the `aux` of one oracle/dense_ref.py pass (float64, bg and colours irrelevant): per Gaussian, whether one of
+    its (pixel, Gaussian) pairs lies within relative NEAR of alpha = 1/255 or of T (1 - alpha) = 1e-4 before the pixel is
+    done -- alpha formed from the EFFECTIVE opacities aux["o_eff"] (o s under antialiasing, o otherwise) -- + the counts
+    (undecided pairs, pairs tested against alpha = 1/255), the empty pixels and the number of pixels that stop early."""
+    dt = torch.float64
+    with torch.no_grad():
+        o = aux["order"]
+        P = aux["o_eff"].shape[0]
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+        pixx, pixy = xs.reshape(-1), ys.reshape(-1)
+        dx = aux["px"].detach()[o][None] - pixx[:, None]
+        dy = aux["py"].detach()[o][None] - pixy[:, None]
+        con = aux["conic"].detach()[o]
+        power = -0.5 * (con[:, 0][None] * dx * dx + con[:, 2][None] * dy * dy) - con[:, 1][None] * dx * dy
+        alpha = torch.clamp_max(aux["o_eff"].detach().to(dt).reshape(-1)[o][None] * torch.exp(power), 0.99)
+        del dx, dy
+        rect = aux["rect"][o]
+        tx, ty = torch.floor(pixx / 16)[:, None], torch.floor(pixy / 16)[:, None]
+        cand = (tx >= rect[:, 0][None]) & (tx < rect[:, 2][None]) & (ty >= rect[:, 1][None]) & (ty < rect[:, 3][None]) & (power <= 0)
+        a = torch.where(aux["include"], alpha, torch.zeros_like(alpha))
+        T = torch.cumprod(1.0 - a, 1)
+        T = torch.cat([torch.ones(H * W, 1, dtype=dt), T[:, :-1]], 1)   # T in front of every entry (constant once the pixel is done)
+        test_T = T * (1.0 - alpha)
+        stop = cand & (alpha >= 1.0 / 255.0) & (test_T < 1e-4)
+        done_before = (torch.cumsum(stop.to(torch.int32), 1) - stop.to(torch.int32)) > 0
+        met = cand & ~done_before
+        near = met & (((255.0 * alpha - 1.0).abs() <= NEAR) | ((alpha >= 1.0 / 255.0) & ((1e4 * test_T - 1.0).abs() <= NEAR)))
+        flag = torch.zeros(P, dtype=torch.bool)
+        flag[o[near.any(0)]] = True
+        empty = ~aux["include"].any(1).view(H, W)
+    return dict(flag=flag.numpy(), near=int(near.sum()), met=int(met.sum()), empty=empty, early=int(stop.any(1).sum()))

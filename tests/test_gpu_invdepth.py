@@ -36,7 +36,7 @@ pytestmark = pytest.mark.gpu
 
 PARITY = 1e-5   # |delta| <= 1e-5 max|g| per tensor: the project's parity bar (README)
 BATCH = 256     # SC_BATCH of csrc/second_colors.hip: list entries staged per trip
-NEAR = 1e-4     # relative distance from a threshold decision within which the float64 reference calls a pair undecided
+NEAR = helpers.NEAR  # relative distance from a threshold decision within which the float64 reference calls a pair undecided
 
 
 def _settings(cam, dev, *tail, sh_degree=3):
@@ -70,16 +70,19 @@ def _grads(names):
     return {k: t.grad.detach().clone() for k, t in names.items() if t.grad is not None}  # (no gradient: not used by the loss)
 
 
-def _one_pass(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot", antialiasing=False, hook=None):
-    """The option: (color, invdepth), gradients by name (+ "colors2" = dL_dcolors of the second image, from the hook)."""
+def _one_pass(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot", antialiasing=False, hook=None, l1_target=None):
+    """The option: (color, invdepth), gradients by name (+ "colors2" = dL_dcolors of the second image, from the hook).
+    `l1_target`: the call also carries the fused L1 loss, added to the loss as it is."""
     import diff_gaussian_rasterization as dgr
     dgr.release_shared_geometry()
     rast = dgr.GaussianRasterizer(_settings(cam, dev, antialiasing, sh_degree=cloud.sh_degree))
     names = _leaves(_inputs(cloud, cam, dev, color_mode, cov_mode))
     names["means2D"] = torch.zeros(cloud.xyz.shape[0], 3, device=dev, requires_grad=True)
-    color, radii, inv = rast(with_invdepth=True, **names)
+    if l1_target is None:
+        (color, radii, inv), loss = rast(with_invdepth=True, **names), 0.0
+    else:
+        color, radii, inv, loss = rast(with_invdepth=True, l1_target=l1_target.to(dev), **names)
     assert tuple(inv.shape) == (1, cam.image_height, cam.image_width)
-    loss = 0.0
     if gC is not None:
         loss = loss + (color * gC.to(dev)).sum()
     if gD is not None:
@@ -98,9 +101,9 @@ def _one_pass(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot", an
     return (color.detach(), inv.detach(), radii), g
 
 
-def _formulation_c(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot", antialiasing=False):
+def _formulation_c(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot", antialiasing=False, l1_target=None):
     """Two rasterizer calls: colour, then colors_precomp = 1/z requiring a gradient (values: the device's own depths, bit
-    for bit; gradient: through z = means3D . V[:3, 2] + V[3, 2])."""
+    for bit; gradient: through z = means3D . V[:3, 2] + V[3, 2]).  `l1_target`: the colour call carries the fused L1 loss."""
     import diff_gaussian_rasterization as dgr
     dgr.release_shared_geometry()
     z_dev, radii_dev, _ = _depths(cloud, cam, dev)
@@ -109,7 +112,11 @@ def _formulation_c(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot
     names["means2D"] = torch.zeros(cloud.xyz.shape[0], 3, device=dev, requires_grad=True)
     V = cam.world_view_transform.to(dev)
     hits0 = dgr._geom_cache.hits
-    color, radii = rast(**names)
+    l1 = 0.0
+    if l1_target is None:
+        color, radii = rast(**names)
+    else:
+        color, radii, l1 = rast(l1_target=l1_target.to(dev), **names)
     zt = names["means3D"] @ V[:3, 2] + V[3, 2]
     soft = torch.where(radii > 0, 1.0 / zt, torch.zeros((), device=dev))
     exact = _inv_colors(z_dev, radii_dev)
@@ -118,7 +125,7 @@ def _formulation_c(cloud, cam, dev, gC, gD, color_mode="sh", cov_mode="scale_rot
     second = {k: v for k, v in names.items() if k not in ("shs", "colors_precomp")}
     img2, _ = rast(colors_precomp=cols2, **second)
     assert dgr._geom_cache.hits - hits0 == 1  # (shared forward)
-    loss = (img2[:1] * gD.to(dev)).sum()
+    loss = (img2[:1] * gD.to(dev)).sum() + l1
     if gC is not None:
         loss = loss + (color * gC.to(dev)).sum()
     loss.backward()
@@ -150,31 +157,8 @@ def _float64(scale_mul, n=None, seed=None, WH=None, frame=0):
                                            cam.full_proj_transform.to(dt), cam.camera_center.to(dt), cloud.xyz.to(dt),
                                            torch.zeros(P, 3, dtype=dt), cloud.opacity.to(dt), colors_precomp=c64,
                                            scales=cloud.scales.to(dt), rotations=cloud.rotations.to(dt))
-        o = aux["order"]
-        ys, xs = torch.meshgrid(torch.arange(h, dtype=dt), torch.arange(w, dtype=dt), indexing="ij")
-        pixx, pixy = xs.reshape(-1), ys.reshape(-1)
-        dx = aux["px"][o][None] - pixx[:, None]
-        dy = aux["py"][o][None] - pixy[:, None]
-        con = aux["conic"][o]
-        power = -0.5 * (con[:, 0][None] * dx * dx + con[:, 2][None] * dy * dy) - con[:, 1][None] * dx * dy
-        alpha = torch.clamp_max(cloud.opacity.to(dt).reshape(-1)[o][None] * torch.exp(power), 0.99)
-        del dx, dy
-        rect = aux["rect"][o]
-        tx, ty = torch.floor(pixx / 16)[:, None], torch.floor(pixy / 16)[:, None]
-        cand = (tx >= rect[:, 0][None]) & (tx < rect[:, 2][None]) & (ty >= rect[:, 1][None]) & (ty < rect[:, 3][None]) & (power <= 0)
-        a = torch.where(aux["include"], alpha, torch.zeros_like(alpha))
-        T = torch.cumprod(1.0 - a, 1)
-        T = torch.cat([torch.ones(h * w, 1, dtype=dt), T[:, :-1]], 1)   # T in front of every entry (constant once the pixel is done)
-        test_T = T * (1.0 - alpha)
-        stop = cand & (alpha >= 1.0 / 255.0) & (test_T < 1e-4)
-        done_before = (torch.cumsum(stop.to(torch.int32), 1) - stop.to(torch.int32)) > 0
-        met = cand & ~done_before
-        near = met & (((255.0 * alpha - 1.0).abs() <= NEAR) | ((alpha >= 1.0 / 255.0) & ((1e4 * test_T - 1.0).abs() <= NEAR)))
-        flag = torch.zeros(P, dtype=torch.bool)
-        flag[o[near.any(0)]] = True
-        empty = ~aux["include"].any(1).view(h, w)
-    return dict(image=img[0].clone(), flag=flag.numpy(), near=int(near.sum()), met=int(met.sum()), visible=(radii > 0).numpy(),
-                empty=empty, early=int(stop.any(1).sum()))
+    u = helpers.undecided_pairs(aux, w, h)   # (alpha from aux["o_eff"]: here the opacities themselves)
+    return dict(image=img[0].clone(), visible=(radii > 0).numpy(), **u)
 
 
 def _assert_bar(name, got, want, setaside=None, cap=None):
