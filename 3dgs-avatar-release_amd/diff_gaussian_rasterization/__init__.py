@@ -50,17 +50,25 @@ _SHARE = os.environ.get("GSPLAT_SHARE_GEOMETRY", "1") != "0"
 _SPECULATE = os.environ.get("GSPLAT_SPECULATE", "1") != "0"
 
 
-class _GeomEntry(object):
-    """Geometry state of ONE forward call (preprocess, sorts, binning), offered to the call that follows it."""
-    __slots__ = ("key", "geom", "binning", "img", "num_rendered", "capacity", "radii", "color_ref", "means2D_id",
-                 "allow_second", "second", "long_lists", "__weakref__")
+class _Frame(object):
+    """State of ONE forward call: its argument block, the state buffers of its geometry (preprocess, sorts, binning) and of
+    its image, and what a second render of that geometry hands over.  Every form of the forward fills one, the call's
+    autograd node owns it (ctx.frame), the backward reads it; a call that may be followed by a second render of its
+    geometry offers it through _GeomCache."""
+    __slots__ = ("key", "a", "keep", "geom", "binning", "img", "radii", "num_rendered", "capacity", "long_lists", "color_ref",
+                 "means2D_id", "allow_second", "second", "__weakref__")
 
-    def __init__(self, key, geom, binning, img, num_rendered, capacity, radii):
-        self.key, self.geom, self.binning, self.img, self.radii = key, geom, binning, img, radii
-        self.num_rendered, self.capacity = num_rendered, capacity  # the frame's pair count / what `binning` is carved for
+    def __init__(self, key, a, keep, geom, img, radii):
+        self.key = key               # _GeomCache.key of the call (None: never on offer)
+        self.a, self.keep = a, keep  # the argument block (pointers into the saved tensors) serves the backward as it is
+        self.geom, self.img, self.radii = geom, img, radii
+        # what the form of the forward fills in: the binning state, the frame's pair count (upstream's num_rendered) and
+        # the pairs the binning state is carved for (>= num_rendered): what the backward is given
+        self.binning, self.num_rendered, self.capacity = None, 0, 0
+        self.long_lists = int(a.long_lists)  # the backward must be told the same (GsFwdArgs.long_lists)
         # for the fused backward of a second render of this geometry (_second_render_dependency): the producing call's
         # image (weak), its means2D, whether it can take a second image along, and what the second call left for it
-        self.color_ref, self.means2D_id, self.allow_second, self.second, self.long_lists = None, None, False, None, 0
+        self.color_ref, self.means2D_id, self.allow_second, self.second = None, None, False, None
 
     def release(self):
         self.key = self.geom = self.binning = self.img = self.radii = None
@@ -86,7 +94,7 @@ class _GeomCache(object):
     also bump the version counters of what they write."""
 
     def __init__(self):
-        self.offer = {}  # device index -> weakref to the _GeomEntry on offer
+        self.offer = {}  # device index -> weakref to the _Frame on offer
         self.hits = 0    # calls served from a previous call's geometry (diagnostics / tests)
 
     @staticmethod
@@ -364,26 +372,131 @@ class _InferenceCtx(object):
         pass
 
 
+# The three ways a frame gets rendered.  Each is given the call's _Frame (argument block, geometry and image state,
+# radii: allocated, not yet written) and the image to render into, and fills in the binning state, the pair count and the
+# capacity.
+
+def _render_shared(fr, hit, color, sptr, debug):
+    """Same geometry and camera as the call just before (`hit`, its frame): new colours only."""
+    L = _lib.load()
+    binning = fr.binning = hit.binning
+    fr.num_rendered, fr.capacity = hit.num_rendered, hit.capacity
+    bin_bytes = binning.numel()
+    fr.radii.copy_(hit.radii)
+    check_qlist = binning.clone() if (debug and bin_bytes) else None
+    _lib.check(L.gs_forward_shared(ctypes.byref(fr.a), hit.geom.data_ptr(), hit.img.data_ptr(), fr.geom.data_ptr(),
+                                   fr.geom.numel(), binning.data_ptr(), bin_bytes, fr.img.data_ptr(), fr.img.numel(),
+                                   fr.capacity, color.data_ptr(), sptr))
+    if check_qlist is not None and not torch.equal(check_qlist, binning):
+        # the shared binning state belongs to the first call's autograd node as well: the second forward
+        # re-records the quadrant lists, which must come out identical for identical geometry
+        raise RuntimeError("diff_gaussian_rasterization: the shared-geometry render changed the binning "
+                           "state it shares with the previous call")
+
+
+def _render_captured(fr, color, dev, sptr):
+    """hipGraph capture (torch.cuda.graph): gs_forward waits for the pair count on the host, which a capture cannot do.
+    The capture-safe form is the two-phase pair at a FIXED capacity -- kernel nodes only; the count stays on the device
+    (captured_forwards() hands out a view of it)."""
+    L = _lib.load()
+    a, geom, img = fr.a, fr.geom, fr.img
+    P, W, H = a.P, a.W, a.H
+    ck = (dev.index, P, W, H)
+    if ck not in _last_count:
+        raise RuntimeError("diff_gaussian_rasterization: run one eager frame of this shape (P=%d, %dx%d) before "
+                           "capturing it into a graph: the binning state of a captured frame has a fixed "
+                           "capacity, sized from the last eager frame's pair count" % (P, W, H))
+    capacity = _capacity_for(max(int(_last_count[ck] * (1.0 + _CAPTURE_SLACK)), 1024))
+    bin_bytes = _size("gs_binning_bytes", capacity, W, H)
+    binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.gs_forward_preprocess(ctypes.byref(a), geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(),
+                                       fr.radii.data_ptr(), None, sptr))
+    _lib.check(L.gs_forward_render(ctypes.byref(a), geom.data_ptr(), geom.numel(), binning.data_ptr(), bin_bytes,
+                                   img.data_ptr(), img.numel(), capacity, color.data_ptr(), sptr))
+    _captured.append((_lib.field_view("gs_geom_field", geom, P, _lib.GS_GEOM_COUNT, nbytes=8).view(torch.int64), capacity))
+    # (the frame's own count is only known on the device)
+    fr.binning, fr.num_rendered, fr.capacity = binning, capacity, capacity
+
+
+def _render_eager(fr, color, dev, sptr):
+    """The binning state is sized by the pair count, which only phase 1 produces.  A buffer for the previous frame's count
+    (+ 1/8) is handed to gs_forward, which enqueues phase 2 right behind phase 1 against that capacity (the kernels read the
+    count on the device) and only then waits for the count: the GPU never idles for it.  Only when the count exceeds the
+    capacity (or there is no estimate yet) does control come back here to allocate and run phase 2 again."""
+    L = _lib.load()
+    a, geom, img = fr.a, fr.geom, fr.img
+    W, H = a.W, a.H
+    ck = (dev.index, a.P, W, H)
+    count = _pinned_count(dev)
+    guess = _last_count.get(ck, 0)
+    capacity = _capacity_for(guess) if (guess and _SPECULATE) else 0
+    bin_bytes = _size("gs_binning_bytes", capacity, W, H) if capacity else 0
+    binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev) if capacity else None
+    nr = ctypes.c_int64(0)
+    rc = L.gs_forward(ctypes.byref(a), geom.data_ptr(), geom.numel(), _lib.ptr(binning), bin_bytes, capacity,
+                      img.data_ptr(), img.numel(), fr.radii.data_ptr(), count.data_ptr(), color.data_ptr(),
+                      ctypes.byref(nr), sptr)
+    num_rendered = int(nr.value)
+    if rc == _lib.GS_E_WORKSPACE:
+        capacity = num_rendered
+        bin_bytes = _size("gs_binning_bytes", capacity, W, H)
+        binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev)
+        rc = L.gs_forward_render(ctypes.byref(a), geom.data_ptr(), geom.numel(), binning.data_ptr(), bin_bytes,
+                                 img.data_ptr(), img.numel(), capacity, color.data_ptr(), sptr)
+    _lib.check(rc)
+    if len(_last_count) > 256:  # (P changes with every densification: keep the table small)
+        _last_count.clear()
+    _last_count[ck] = num_rendered
+    fr.binning, fr.num_rendered, fr.capacity = binning, num_rendered, capacity
+
+
+def _render_invdepth(fr, dev, sptr):
+    """Upstream's inverse-depth image, sum alpha T / z: a second render of THIS call's geometry (recorded quadrant lists,
+    same alpha and T) with the colours (1/z, 1/z, 1/z) over a zero background; z = the view-space depths the forward
+    stored, 1/z = 0 for the Gaussians it culled.  Returns the image [1, H, W] and the render's states, which stay with
+    this call's node: its backward differentiates both images in one pass (gs_backward_with_second with dL_dcolors)."""
+    L = _lib.load()
+    a, geom, img, binning = fr.a, fr.geom, fr.img, fr.binning
+    P = a.P
+    depths = _lib.field_view("gs_geom_field", geom, P, _lib.GS_GEOM_DEPTHS, nbytes=4 * P).view(torch.float32)
+    invz = torch.where(fr.radii > 0, 1.0 / depths, torch.zeros((), dtype=torch.float32, device=dev))
+    colors2 = invz.unsqueeze(1).expand(P, 3).contiguous()
+    bg2 = torch.zeros(3, dtype=torch.float32, device=dev)
+    a2 = _lib.GsFwdArgs.from_buffer_copy(a)
+    a2.shs, a2.M, a2.colors_precomp, a2.bg = None, 0, colors2.data_ptr(), bg2.data_ptr()
+    a2.frame_stats = a2.l1_target = a2.l1_loss = a2.l1_grad = None
+    geom2 = torch.empty_like(geom)  # (what gs_forward_shared recolours into; nothing reads it afterwards: DESIGN.md 5b)
+    img2 = torch.empty_like(img)
+    color2 = torch.empty(3, a.H, a.W, dtype=torch.float32, device=dev)
+    _lib.check(L.gs_forward_shared(ctypes.byref(a2), geom.data_ptr(), img.data_ptr(), geom2.data_ptr(), geom2.numel(),
+                                   _lib.ptr(binning), binning.numel() if binning is not None else 0,
+                                   img2.data_ptr(), img2.numel(), fr.capacity, color2.data_ptr(), sptr))
+    # the recolouring launch has set this geometry's "a second render's colours are not all ones" word; cleared
+    # again, so that a following call's shared render (the reference's opacity pass) finds what it would have
+    # found without the flag
+    words = _lib.field_view("gs_geom_field", geom, P, _lib.GS_GEOM_COUNT, nbytes=8 * (_lib.GS_COUNT_NOT_ONES + 1))
+    words[8 * _lib.GS_COUNT_NOT_ONES:].zero_()
+    return color2[:1], (colors2, color2, img2)  # (geom2 holds nothing the backward reads)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, with_opacity=False, dep=None, l1_target=None, with_invdepth=False):
-        if not raster_settings.debug:
-            return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                                cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target, with_invdepth)
-        # upstream's debug mode: the arguments are kept aside and written to snapshot_fw.dump if the native call fails
-        args = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         try:
             return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                                 cov3Ds_precomp, raster_settings, with_opacity, dep, l1_target, with_invdepth)
         except Exception:
-            _dump_snapshot("snapshot_fw.dump", raster_settings, args)
-            print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+            if raster_settings.debug:  # upstream's debug mode: the arguments are written to snapshot_fw.dump
+                _dump_snapshot("snapshot_fw.dump", raster_settings,
+                               (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
+                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
             raise
 
     @staticmethod
     def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                  raster_settings, with_opacity=False, dep=None, l1_target=None, with_invdepth=False):
+        ctx.raster_settings = raster_settings
         ctx.with_opacity = bool(with_opacity)
         ctx.with_invdepth = bool(with_invdepth)
         ctx.l1_target = None
@@ -393,7 +506,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         # outputs nothing downstream differentiates (always: radii) arrive as None in backward instead of as freshly
         # filled zero tensors -- one fill launch over P ints per step otherwise
         ctx.set_materialize_grads(False)
-        L = _lib.load()
         means3D = _f32c(means3D, "means3D")
         if means3D is None:
             raise RuntimeError("diff_gaussian_rasterization: means3D is empty")
@@ -438,198 +550,86 @@ class _RasterizeGaussians(torch.autograd.Function):
             hit = _geom_cache.take(dev, gkey) if (share and l1_target is None and not ctx.with_invdepth) else None
             if not share or l1_target is not None or ctx.with_invdepth:
                 _geom_cache.offer.pop(dev.index, None)
-            ctx.geom_entry = None
             if hit is not None:
                 # a second render of that call's geometry runs with ITS long_lists (the statistics word may have changed
                 # since): the two image states then have one layout, which the all-ones render and the one-pass backward need
                 a.long_lists = int(hit.long_lists)
-            geom_bytes = _size("gs_geom_bytes", P)
             ik = ("img", W, H, int(a.long_lists))
             img_bytes = _sizes.get(ik)
             if img_bytes is None:
-                img_bytes = _sizes[ik] = _lib.nbytes(L.gs_image_bytes_for, ctypes.byref(a))
-            geom = torch.empty(geom_bytes, dtype=torch.uint8, device=dev)
-            img = torch.empty(img_bytes, dtype=torch.uint8, device=dev)
-            radii = torch.empty(P, dtype=torch.int32, device=dev)
-            if hit is not None:
-                # same geometry and camera as the call just before: new colours only
-                num_rendered, capacity = hit.num_rendered, hit.capacity
-                binning = hit.binning
-                if (dep is not None and hit.allow_second and hit.color_ref is not None and hit.color_ref() is dep
-                        and hit.long_lists == int(a.long_lists)):
-                    ctx.defer_to = hit  # this call's backward hands its gradient to the producing call's (below)
-                bin_bytes = binning.numel()
-                radii.copy_(hit.radii)
-                color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-                check_qlist = binning.clone() if (raster_settings.debug and bin_bytes) else None
-                _lib.check(L.gs_forward_shared(ctypes.byref(a), hit.geom.data_ptr(), hit.img.data_ptr(),
-                                               geom.data_ptr(), geom_bytes, binning.data_ptr(), bin_bytes, img.data_ptr(),
-                                               img_bytes, capacity, color.data_ptr(), sptr))
-                if check_qlist is not None and not torch.equal(check_qlist, binning):
-                    # the shared binning state belongs to the first call's autograd node as well: the second forward
-                    # re-records the quadrant lists, which must come out identical for identical geometry
-                    raise RuntimeError("diff_gaussian_rasterization: the shared-geometry render changed the binning "
-                                       "state it shares with the previous call")
-                return _RasterizeGaussians._finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp,
-                                                   opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning,
-                                                   img, color, dev, a, sptr, keep)
+                img_bytes = _sizes[ik] = _lib.nbytes(_lib.load().gs_image_bytes_for, ctypes.byref(a))
+            fr = _Frame(gkey, a, keep, torch.empty(_size("gs_geom_bytes", P), dtype=torch.uint8, device=dev),
+                        torch.empty(img_bytes, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev))
             color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-            if capturing:
-                # hipGraph capture (torch.cuda.graph): gs_forward waits for the pair count on the host, which a capture
-                # cannot do.  The capture-safe form is the two-phase pair at a FIXED capacity -- kernel nodes only; the
-                # count stays on the device (captured_forwards() hands out a view of it)
-                ck = (dev.index, P, W, H)
-                if ck not in _last_count:
-                    raise RuntimeError("diff_gaussian_rasterization: run one eager frame of this shape (P=%d, %dx%d) before "
-                                       "capturing it into a graph: the binning state of a captured frame has a fixed "
-                                       "capacity, sized from the last eager frame's pair count" % (P, W, H))
-                guess = _last_count[ck]
-                capacity = _capacity_for(max(int(guess * (1.0 + _CAPTURE_SLACK)), 1024))
-                bin_bytes = _size("gs_binning_bytes", capacity, W, H)
-                binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.gs_forward_preprocess(ctypes.byref(a), geom.data_ptr(), geom_bytes, img.data_ptr(), img_bytes,
-                                                   radii.data_ptr(), None, sptr))
-                _lib.check(L.gs_forward_render(ctypes.byref(a), geom.data_ptr(), geom_bytes, binning.data_ptr(), bin_bytes,
-                                               img.data_ptr(), img_bytes, capacity, color.data_ptr(), sptr))
-                cptr = ctypes.c_void_p()
-                _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_COUNT, ctypes.byref(cptr)))
-                off = int(cptr.value) - geom.data_ptr()
-                _captured.append((geom[off:off + 8].view(torch.int64), capacity))
-                num_rendered = capacity  # (the frame's own count is only known on the device)
+            if hit is not None:
+                if (dep is not None and hit.allow_second and hit.color_ref is not None and hit.color_ref() is dep
+                        and hit.long_lists == fr.long_lists):
+                    ctx.defer_to = hit  # this call's backward hands its gradient to the producing call's (_backward)
+                _render_shared(fr, hit, color, sptr, raster_settings.debug)
+            else:
+                if capturing:
+                    _render_captured(fr, color, dev, sptr)
+                else:
+                    _render_eager(fr, color, dev, sptr)
                 if share:
-                    ctx.geom_entry = _GeomEntry(gkey, geom, binning, img, num_rendered, capacity, radii)
-                    ctx.geom_entry.color_ref = weakref.ref(color)
-                    ctx.geom_entry.means2D_id = id(means2D_in)
-                    ctx.geom_entry.allow_second = not ctx.with_opacity and not ctx.with_invdepth
-                    ctx.geom_entry.long_lists = int(a.long_lists)
-                    _geom_cache.put(dev, ctx.geom_entry)
-                return _RasterizeGaussians._finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp,
-                                                   opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img,
-                                                   color, dev, a, sptr, keep, l1)
-            count = _pinned_count(dev)
-            # The binning state is sized by the pair count, which only phase 1 produces.  A buffer for the
-            # previous frame's count (+ 1/8) is handed to gs_forward, which enqueues phase 2 right behind phase 1
-            # against that capacity (the kernels read the count on the device) and only then waits for the count:
-            # the GPU never idles for it.  Only when the count exceeds the capacity (or there is no estimate yet)
-            # does control come back here to allocate and run phase 2 again.
-            guess = _last_count.get((dev.index, P, W, H), 0)
-            capacity = _capacity_for(guess) if (guess and _SPECULATE) else 0
-            bin_bytes = _size("gs_binning_bytes", capacity, W, H) if capacity else 0
-            binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev) if capacity else None
-            nr = ctypes.c_int64(0)
-            rc = L.gs_forward(ctypes.byref(a), geom.data_ptr(), geom_bytes, _lib.ptr(binning), bin_bytes, capacity,
-                              img.data_ptr(), img_bytes, radii.data_ptr(), count.data_ptr(), color.data_ptr(),
-                              ctypes.byref(nr), sptr)
-            num_rendered = int(nr.value)
-            if rc == _lib.GS_E_WORKSPACE:
-                capacity = num_rendered
-                bin_bytes = _size("gs_binning_bytes", capacity, W, H)
-                binning = torch.empty(bin_bytes, dtype=torch.uint8, device=dev)
-                rc = L.gs_forward_render(ctypes.byref(a), geom.data_ptr(), geom_bytes, binning.data_ptr(), bin_bytes,
-                                         img.data_ptr(), img_bytes, capacity, color.data_ptr(), sptr)
-            _lib.check(rc)
-            if len(_last_count) > 256:  # (P changes with every densification: keep the table small)
-                _last_count.clear()
-            _last_count[(dev.index, P, W, H)] = num_rendered
-            if share:
-                # offered to the next call; owned by this call's autograd node (ctx), not by the cache
-                ctx.geom_entry = _GeomEntry(gkey, geom, binning, img, num_rendered, capacity, radii)
-                ctx.geom_entry.color_ref = weakref.ref(color)  # (the tensor this call returns: autograd tracks it)
-                ctx.geom_entry.means2D_id = id(means2D_in)
-                ctx.geom_entry.allow_second = not ctx.with_opacity and not ctx.with_invdepth
-                ctx.geom_entry.long_lists = int(a.long_lists)
-                _geom_cache.put(dev, ctx.geom_entry)
-            return _RasterizeGaussians._finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp,
-                                               opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img, color,
-                                               dev, a, sptr, keep, l1)
+                    # offered to the next call; owned by this call's autograd node (ctx.frame), not by the cache
+                    fr.color_ref = weakref.ref(color)  # (the tensor this call returns: autograd tracks it)
+                    fr.means2D_id = id(means2D_in)
+                    fr.allow_second = not ctx.with_opacity and not ctx.with_invdepth
+                    _geom_cache.put(dev, fr)
+            out = _RasterizeGaussians._finish(
+                ctx, fr, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), color, l1, sptr)
+            if fr.color_ref is None and not inference:
+                fr.release()  # not on offer: its buffers live as long as the saved tensors (which hooks may have moved)
+            return out
 
     @staticmethod
-    def _finish(ctx, raster_settings, num_rendered, capacity, means3D, sh, colors_precomp, opacities, scales, rotations,
-                cov3Ds_precomp, radii, geom, binning, img, color, dev, a, sptr, keep=None, l1=None):
+    def _finish(ctx, fr, inputs, color, l1, sptr):
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = inputs
+        dev = color.device
         opacity = None
         if ctx.with_opacity:
             # the opacity render is (1 - final_T) + final_T * bg[0]: the forward that just ran holds final_T
-            L = _lib.load()
-            H, W = int(raster_settings.image_height), int(raster_settings.image_width)
-            opacity = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.gs_opacity_image(ctypes.byref(a), img.data_ptr(), img.numel(), opacity.data_ptr(), sptr))
-        invdepth = None
-        second = ()
-        if ctx.with_invdepth:
-            # upstream's inverse-depth image, sum alpha T / z: a second render of THIS call's geometry (recorded quadrant
-            # lists, same alpha and T) with the colours (1/z, 1/z, 1/z) over a zero background; z = the view-space depths
-            # the forward stored, 1/z = 0 for the Gaussians it culled.  The render's states stay with this node: its
-            # backward differentiates both images in one pass (gs_backward_with_second with dL_dcolors)
-            L = _lib.load()
-            H, W = int(raster_settings.image_height), int(raster_settings.image_width)
-            P = int(means3D.shape[0])
-            fptr = ctypes.c_void_p()
-            _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_DEPTHS, ctypes.byref(fptr)))
-            off = int(fptr.value) - geom.data_ptr()
-            depths = geom[off:off + 4 * P].view(torch.float32)
-            invz = torch.where(radii > 0, 1.0 / depths, torch.zeros((), dtype=torch.float32, device=dev))
-            colors2 = invz.unsqueeze(1).expand(P, 3).contiguous()
-            bg2 = torch.zeros(3, dtype=torch.float32, device=dev)
-            a2 = _lib.GsFwdArgs.from_buffer_copy(a)
-            a2.shs, a2.M, a2.colors_precomp, a2.bg = None, 0, colors2.data_ptr(), bg2.data_ptr()
-            a2.frame_stats = a2.l1_target = a2.l1_loss = a2.l1_grad = None
-            geom2 = torch.empty_like(geom)  # (what gs_forward_shared recolours into; nothing reads it afterwards: DESIGN.md 5b)
-            img2 = torch.empty_like(img)
-            color2 = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.gs_forward_shared(ctypes.byref(a2), geom.data_ptr(), img.data_ptr(), geom2.data_ptr(), geom2.numel(),
-                                           _lib.ptr(binning), binning.numel() if binning is not None else 0,
-                                           img2.data_ptr(), img2.numel(), capacity, color2.data_ptr(), sptr))
-            # the recolouring launch has set this geometry's "a second render's colours are not all ones" word; cleared
-            # again, so that a following call's shared render (the reference's opacity pass) finds what it would have
-            # found without the flag
-            _lib.check(L.gs_geom_field(geom.data_ptr(), P, _lib.GS_GEOM_COUNT, ctypes.byref(fptr)))
-            off = int(fptr.value) - geom.data_ptr() + 8 * _lib.GS_COUNT_NOT_ONES
-            geom[off:off + 8].zero_()
-            invdepth = color2[:1]
-            second = (colors2, color2, img2)  # (geom2 holds nothing the backward reads)
-        ctx.raster_settings = raster_settings
-        ctx.long_lists = int(a.long_lists)  # the backward must be told the same (GsFwdArgs.long_lists)
-        ctx.fwd_args = (a, keep)  # the argument block (pointers into the saved tensors) serves the backward as it is
-        ctx.num_rendered = num_rendered  # the frame's pair count (upstream's num_rendered)
-        ctx.capacity = capacity          # pairs the binning state is carved for (>= num_rendered): what the backward is given
+            opacity = torch.empty(1, fr.a.H, fr.a.W, dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().gs_opacity_image(ctypes.byref(fr.a), fr.img.data_ptr(), fr.img.numel(), opacity.data_ptr(),
+                                                    sptr))
+        invdepth, second = _render_invdepth(fr, dev, sptr) if ctx.with_invdepth else (None, ())
+        ctx.frame = fr
+        ctx.long_lists = fr.long_lists  # (what tests and tools read off `color.grad_fn`)
         ctx.present = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         empty = torch.empty(0, device=dev)
         ctx.save_for_backward(means3D, sh if sh is not None else empty,
                               colors_precomp if colors_precomp is not None else empty, opacities,
                               scales if scales is not None else empty, rotations if rotations is not None else empty,
-                              cov3Ds_precomp if cov3Ds_precomp is not None else empty, radii, geom, binning, img, color,
-                              *second)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, opacity, l1, invdepth
+                              cov3Ds_precomp if cov3Ds_precomp is not None else empty, fr.radii, fr.geom, fr.binning, fr.img,
+                              color, *second)
+        ctx.mark_non_differentiable(fr.radii)
+        return color, fr.radii, opacity, l1, invdepth
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None, grad_invdepth=None):
-        if not ctx.raster_settings.debug:
-            return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1, grad_invdepth)
         try:
             return _RasterizeGaussians._backward(ctx, grad_out_color, _grad_radii, grad_out_opacity, grad_l1, grad_invdepth)
         except Exception:
-            _dump_snapshot("snapshot_bw.dump", ctx.raster_settings, tuple(ctx.saved_tensors[:8]) + (grad_out_color,))
-            print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            if ctx.raster_settings.debug:
+                _dump_snapshot("snapshot_bw.dump", ctx.raster_settings, tuple(ctx.saved_tensors[:8]) + (grad_out_color,))
+                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
             raise
 
     @staticmethod
     def _backward(ctx, grad_out_color, _grad_radii, grad_out_opacity=None, grad_l1=None, grad_invdepth=None):
         L = _lib.load()
-        tgt = getattr(ctx, "defer_to", None)
+        fr, tgt = ctx.frame, ctx.defer_to
         if tgt is not None and tgt.geom is not None and grad_out_color is not None:
             # a second render of another call's geometry (see _second_render_dependency): that call's backward, which runs
             # after this one, differentiates both images in one pass
             saved = ctx.saved_tensors
             tgt.second = dict(colors=saved[2], out_color=saved[11], grad=_f32c(grad_out_color, "grad_out_color"), img=saved[10],
-                              long_lists=ctx.long_lists)
+                              long_lists=fr.long_lists)
             return (None,) * 13
-        entry = getattr(ctx, "geom_entry", None)
-        second = None
-        if entry is not None:  # a render after this backward (e.g. after an optimiser step) must not meet this state
-            second, entry.second = entry.second, None
-            entry.release()
-            ctx.geom_entry = None
+        # a render after this backward (e.g. after an optimiser step) must not meet this state
+        second, fr.second = fr.second, None
+        fr.release()
         (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img,
          color) = ctx.saved_tensors[:12]
         has_sh, has_col, has_sr, has_cov = ctx.present
@@ -637,24 +637,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         P = int(means3D.shape[0])
         W, H = int(settings.image_width), int(settings.image_height)
-        D = ctx.capacity
+        D = fr.capacity
         use_l1 = ctx.l1_target is not None and grad_l1 is not None
         # the inverse-depth image's gradient, if that image was used downstream (None: today's plain path, bit for bit)
-        g_inv = _f32c(grad_invdepth, "grad_invdepth") if (getattr(ctx, "with_invdepth", False) and grad_invdepth is not None) else None
+        g_inv = _f32c(grad_invdepth, "grad_invdepth") if (ctx.with_invdepth and grad_invdepth is not None) else None
         if grad_out_color is None and not use_l1:  # only the opacity / inverse-depth render was used downstream
             grad_out_color = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
         g = _f32c(grad_out_color, "grad_out_color") if grad_out_color is not None else None
         g_l1 = _f32c(grad_l1, "grad_l1") if use_l1 else None
         g_op = _f32c(grad_out_opacity, "grad_out_opacity") if (ctx.with_opacity and grad_out_opacity is not None) else None
         with _lib.on_device(dev):
-            a, _keep = ctx.fwd_args  # the forward's argument block: the same tensors (saved above), the same long_lists
+            a, _keep = fr.a, fr.keep  # the forward's argument block: the same tensors (saved above), the same long_lists
             if (a.means3D != means3D.data_ptr() or a.opacities != opacities.data_ptr()
                     or (has_sh and a.shs != sh.data_ptr()) or (has_sr and a.scales != scales.data_ptr())):
                 # the saved tensors came back in other storage (saved-tensor hooks: offloading, checkpointing)
                 _keep = []
                 a = _make_args(settings, means3D, sh if has_sh else None, colors_precomp if has_col else None, opacities,
                                scales if has_sr else None, rotations if has_sr else None,
-                               cov3Ds_precomp if has_cov else None, _keep, long_lists=ctx.long_lists)
+                               cov3Ds_precomp if has_cov else None, _keep, long_lists=fr.long_lists)
             # the fused L1 loss: dL/d(image) of it is formed per pixel inside the backward's render pass (no gradient image)
             a.l1_target = ctx.l1_target.data_ptr() if use_l1 else None
             a.l1_loss = None  # (the forward's output; the backward does not touch it)
@@ -675,20 +675,34 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_rot = torch.empty(P, 4, **f) if has_sr else None
             gr = _lib.GsGrads(_lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_sh), _lib.ptr(d_colors),
                               _lib.ptr(d_opacity), _lib.ptr(d_scales), _lib.ptr(d_rot), _lib.ptr(d_cov3D))
+            # one backward pass, three entry points: they share the arguments before and behind the one that differs
+            lead = (ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(), binning.data_ptr(), binning.numel(),
+                    img.data_ptr(), img.numel(), D, color.data_ptr(), gp)
+            tail = (scratch.data_ptr(), scratch_bytes, ctypes.byref(gr), sptr)
+            si = None
             if g_inv is not None:
                 # both images in one pass: the second image is this node's own inverse-depth render, whose colours (1/z)
                 # DO depend on an input -- dL_dcolors of the second image is asked for, and the chain through z is closed
-                # here: d(1/z)/d(means3D) = -1/z^2 * viewmatrix[:3, 2]
+                # below: d(1/z)/d(means3D) = -1/z^2 * viewmatrix[:3, 2]
                 colors2, color2, img2 = ctx.saved_tensors[12:15]
                 g2 = torch.zeros(3, H, W, **f)
                 g2[0].copy_(g_inv.reshape(H, W))
                 d_colors2 = torch.empty(P, 3, **f)
                 si = _lib.GsSecondImage(colors2.data_ptr(), color2.data_ptr(), g2.data_ptr(), img2.data_ptr(), img2.numel(),
-                                        ctx.long_lists, d_colors2.data_ptr())
-                _lib.check(L.gs_backward_with_second(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
-                                                     binning.data_ptr(), binning.numel(), img.data_ptr(), img.numel(), D,
-                                                     color.data_ptr(), gp, ctypes.byref(si), scratch.data_ptr(),
-                                                     scratch_bytes, ctypes.byref(gr), sptr))
+                                        fr.long_lists, d_colors2.data_ptr())
+            elif second is not None and g_op is None:
+                # what the second render of this geometry left here (above): both images in one pass
+                si = _lib.GsSecondImage(second["colors"].data_ptr(), second["out_color"].data_ptr(), second["grad"].data_ptr(),
+                                        second["img"].data_ptr(), second["img"].numel(), int(second["long_lists"]))
+            if si is not None:
+                fn, mid = L.gs_backward_with_second, (ctypes.byref(si),)
+            elif g_op is None:
+                fn, mid = L.gs_backward, ()
+            else:
+                # the opacity render's gradient rides along as a fourth channel of the same backward pass
+                fn, mid = L.gs_backward_with_opacity, (g_op.data_ptr(),)
+            _lib.check(fn(*lead, *mid, *tail))
+            if g_inv is not None:
                 # (tests: gsplat_mi355.debug.second_colors_hook, if that module is loaded)
                 hook = getattr(sys.modules.get("gsplat_mi355.debug"), "second_colors_hook", None)
                 if hook is not None:
@@ -696,24 +710,6 @@ class _RasterizeGaussians(torch.autograd.Function):
                 invz = colors2[:, 0]
                 view = _f32c(settings.viewmatrix.to(dev), "viewmatrix")
                 d_means3D.addcmul_((d_colors2.sum(1) * invz * invz).unsqueeze(1), view[:3, 2].unsqueeze(0), value=-1.0)
-            elif second is not None and g_op is None:
-                si = _lib.GsSecondImage(second["colors"].data_ptr(), second["out_color"].data_ptr(), second["grad"].data_ptr(),
-                                        second["img"].data_ptr(), second["img"].numel(), int(second["long_lists"]))
-                _lib.check(L.gs_backward_with_second(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
-                                                     binning.data_ptr(), binning.numel(), img.data_ptr(), img.numel(), D,
-                                                     color.data_ptr(), gp, ctypes.byref(si), scratch.data_ptr(),
-                                                     scratch_bytes, ctypes.byref(gr), sptr))
-            elif g_op is None:
-                _lib.check(L.gs_backward(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
-                                         binning.data_ptr(), binning.numel(), img.data_ptr(), img.numel(), D,
-                                         color.data_ptr(), gp, scratch.data_ptr(), scratch_bytes,
-                                         ctypes.byref(gr), sptr))
-            else:
-                # the opacity render's gradient rides along as a fourth channel of the same backward pass
-                _lib.check(L.gs_backward_with_opacity(ctypes.byref(a), radii.data_ptr(), geom.data_ptr(), geom.numel(),
-                                                      binning.data_ptr(), binning.numel(), img.data_ptr(), img.numel(), D,
-                                                      color.data_ptr(), gp, g_op.data_ptr(), scratch.data_ptr(),
-                                                      scratch_bytes, ctypes.byref(gr), sptr))
         return (d_means3D, d_means2D, d_sh, d_colors if has_col else None, d_opacity, d_scales, d_rot,
                 d_cov3D if has_cov else None, None, None, None, None, None)
 

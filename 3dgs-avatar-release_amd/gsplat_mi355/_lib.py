@@ -377,6 +377,17 @@ def nbytes(fn, *args):
     return int(out.value)
 
 
+def field_view(fn_name, buf, *args, nbytes):
+    """The `nbytes` of a field of the state buffer `buf` (a uint8 tensor), as a view of it.  `fn_name`: gs_geom_field,
+    gs_binning_field or gs_image_field; `args`: what that takes between the buffer and the result (the sizes the buffer was
+    carved for, the field's id)."""
+    out = c_void_p(0)
+    check(getattr(load(), fn_name)(buf.data_ptr(), *args, ctypes.byref(out)))
+    off = int(out.value) - buf.data_ptr()
+    assert 0 <= off and off + nbytes <= buf.numel()
+    return buf[off:off + nbytes]
+
+
 class _OnDevice(object):
     __slots__ = ("idx", "prev")
 

@@ -14,13 +14,6 @@ from diff_gaussian_rasterization import GaussianRasterizationSettings, _make_arg
 second_colors_hook = None
 
 
-def _view(owner, ptr, nbytes, dtype):
-    """numpy copy of `nbytes` at device address `ptr`, which lies inside the uint8 tensor `owner`."""
-    off = ptr - owner.data_ptr()
-    assert 0 <= off and off + nbytes <= owner.numel()
-    return owner[off:off + nbytes].cpu().numpy().view(dtype).copy()
-
-
 def forward_state(settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                   cov3D_precomp=None):
     """Runs preprocess + render through the C ABI; returns dict(color, radii, geom=..., binning=..., image=...)."""
@@ -58,40 +51,39 @@ def forward_state(settings, means3D, opacities, shs=None, colors_precomp=None, s
         stream.synchronize()
         pairs_valid, pairs_walked = (int(v) for v in counts.cpu())
 
-        def field(fn, *args):
-            out = ctypes.c_void_p(0)
-            _lib.check(fn(*args, ctypes.byref(out)))
-            return out.value
+        def field(dtype, nbytes, *where):
+            """numpy copy of a field of a state buffer; `where`: the entry point, the buffer, its sizes, the field's id."""
+            return _lib.field_view(*where, nbytes=nbytes).cpu().numpy().view(dtype).copy()
         gx, gy = (W + 15) // 16, (H + 15) // 16
         g = dict(
-            depths=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_DEPTHS), 4 * P, np.float32),
-            tiles_touched=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_TILES), 4 * P, np.uint32),
-            rec=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_REC), 48 * P, np.float32).reshape(P, 12),
-            clamped=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_CLAMPED), 4 * P, np.uint32),
-            sorted_idx=_view(geom, field(L.gs_geom_field, geom.data_ptr(), P, _lib.GS_GEOM_SORTED_IDX), 4 * P, np.uint32),
+            depths=field(np.float32, 4 * P, "gs_geom_field", geom, P, _lib.GS_GEOM_DEPTHS),
+            tiles_touched=field(np.uint32, 4 * P, "gs_geom_field", geom, P, _lib.GS_GEOM_TILES),
+            rec=field(np.float32, 48 * P, "gs_geom_field", geom, P, _lib.GS_GEOM_REC).reshape(P, 12),
+            clamped=field(np.uint32, 4 * P, "gs_geom_field", geom, P, _lib.GS_GEOM_CLAMPED),
+            sorted_idx=field(np.uint32, 4 * P, "gs_geom_field", geom, P, _lib.GS_GEOM_SORTED_IDX),
         ) if P > 0 else {}
         b = dict(
-            point_list=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, _lib.GS_BIN_POINT_LIST), 4 * D, np.uint32),
+            point_list=field(np.uint32, 4 * D, "gs_binning_field", binning, D, W, H, _lib.GS_BIN_POINT_LIST),
             # the quadrants' compacted lists: quadrant q of tile t at [4 ranges[t, 0] + q n_t, ... + qcount[t, q])
-            qlist=_view(binning, field(L.gs_binning_field, binning.data_ptr(), D, W, H, _lib.GS_BIN_QLIST), 16 * D, np.uint32),
+            qlist=field(np.uint32, 16 * D, "gs_binning_field", binning, D, W, H, _lib.GS_BIN_QLIST),
         ) if D > 0 else dict(point_list=np.zeros(0, np.uint32), qlist=np.zeros(0, np.uint32))
         im = dict(
-            ranges=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_RANGES), 8 * gx * gy, np.uint32).reshape(-1, 2),
-            n_contrib=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_N_CONTRIB), 4 * W * H, np.uint32).reshape(H, W),
-            final_T=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_FINAL_T), 4 * W * H, np.float32).reshape(H, W),
-            qcount=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_QCOUNT), 16 * gx * gy, np.uint32).reshape(-1, 4),
+            ranges=field(np.uint32, 8 * gx * gy, "gs_image_field", img, W, H, _lib.GS_IMG_RANGES).reshape(-1, 2),
+            n_contrib=field(np.uint32, 4 * W * H, "gs_image_field", img, W, H, _lib.GS_IMG_N_CONTRIB).reshape(H, W),
+            final_T=field(np.float32, 4 * W * H, "gs_image_field", img, W, H, _lib.GS_IMG_FINAL_T).reshape(H, W),
+            qcount=field(np.uint32, 16 * gx * gy, "gs_image_field", img, W, H, _lib.GS_IMG_QCOUNT).reshape(-1, 4),
             # launch order of the tiles (heaviest first); bit 31: rendered by four waves per quadrant (small images)
-            order=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_ORDER), 4 * gx * gy, np.uint32),
+            order=field(np.uint32, 4 * gx * gy, "gs_image_field", img, W, H, _lib.GS_IMG_ORDER),
         )
         # the chunk-parallel forward's work list and hand-off words (gs_tuning "fwd4" = 2 on a small image; else absent)
         probe = ctypes.c_void_p(0)
         if L.gs_image_field(img.data_ptr(), W, H, _lib.GS_IMG_CW_HDR, ctypes.byref(probe)) == 0:  # GS_OK
-            hdr = _view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_HDR), 64, np.uint32)
+            hdr = field(np.uint32, 64, "gs_image_field", img, W, H, _lib.GS_IMG_CW_HDR)
             nu = int(hdr[0])
             im["chunks"] = dict(
                 hdr=hdr,
-                units=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_UNITS), 8 * nu, np.uint32).reshape(-1, 2),
-                flags=_view(img, field(L.gs_image_field, img.data_ptr(), W, H, _lib.GS_IMG_CW_FLAG), 16 * nu, np.uint32))
+                units=field(np.uint32, 8 * nu, "gs_image_field", img, W, H, _lib.GS_IMG_CW_UNITS).reshape(-1, 2),
+                flags=field(np.uint32, 16 * nu, "gs_image_field", img, W, H, _lib.GS_IMG_CW_FLAG))
     # the tile of every list entry: the lists are stored tile after tile, so the ranges say it (upstream keeps the tile
     # id in the high half of its sort keys)
     r = im["ranges"].astype(np.int64)

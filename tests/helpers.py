@@ -18,6 +18,26 @@ def cloud_and_camera(n, W, H, sh_degree=3, seed=0, frame=0, dist2_fn=None, heavy
     return cloud, cam
 
 
+class _CallCounter(object):
+    """Stands in for the loaded C library and counts the calls per entry point (which backward did the step take?).
+    A subclass that wants more of a call than its name overrides `_note`."""
+
+    def __init__(self, lib):
+        import collections
+        self._lib, self.calls = lib, collections.Counter()
+
+    def _note(self, name, args):
+        self.calls[name] += 1
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def counted(*a):
+            self._note(name, a)
+            return fn(*a)
+        return counted
+
+
 POSES = {  # name -> (yaw, pitch, roll), T, (kx, ky): what cloud_and_camera's orbit camera never has
     # every entry of the 3x3 block non-zero, fx != fy, off-axis translation
     "general": ((0.7, -0.4, 0.9), (0.3, -0.2, 3.2), (1.0, 1.31)),

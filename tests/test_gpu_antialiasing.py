@@ -20,6 +20,7 @@ import torch
 
 import antialias_ref as ref
 import helpers
+from helpers import _CallCounter
 
 pytestmark = pytest.mark.gpu
 
@@ -157,22 +158,6 @@ def test_forward_is_bitwise_the_default_path_on_the_effective_opacities(tile_rec
         assert on["D"] == plain["D"]  # the 3-sigma square does not depend on the opacity
     else:
         assert on["D"] < plain["D"]
-
-
-class _CallCounter(object):
-    """Stands in for the loaded C library and counts the calls per entry point (which backward did the step take?)."""
-
-    def __init__(self, lib):
-        import collections
-        self._lib, self.calls = lib, collections.Counter()
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def counted(*a):
-            self.calls[name] += 1
-            return fn(*a)
-        return counted
 
 
 _BACKWARD_OF = {"plain": "gs_backward", "with-opacity": "gs_backward_with_opacity", "two-call": "gs_backward_with_second"}

@@ -124,7 +124,8 @@ def _run(oracle, monkeypatch, m, mode, cloud_cam=None, check_lists=True):
     with arbitrary constant colours; 3: a second image of colours one), gradients against the oracle's pass(es)."""
     import diff_gaussian_rasterization as dgr
     from gsplat_mi355 import _lib, debug
-    from test_gpu_parity import _attribute, _bulk_close, _CallCounter, _settings
+    from helpers import _CallCounter
+    from test_gpu_parity import _attribute, _bulk_close, _settings
     dev = torch.device("cuda:0")
     cloud, cam = cloud_cam or _stack(m, seed=100 + m)
     n = cloud.xyz.shape[0]

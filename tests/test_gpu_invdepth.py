@@ -30,7 +30,8 @@ import pytest
 import torch
 
 import helpers
-from test_gpu_antialiasing import BEHIND, BORDER, CLAMP, H, W, _CallCounter, _inputs, _scene, tile_rect  # noqa: F401
+from helpers import _CallCounter
+from test_gpu_antialiasing import BEHIND, BORDER, CLAMP, H, W, _inputs, _scene, tile_rect  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -27,6 +27,7 @@ import pytest
 import torch
 
 import helpers
+from helpers import _CallCounter
 
 pytestmark = pytest.mark.gpu
 
@@ -879,22 +880,6 @@ def test_full_size_trained_avatar_shaped_frame_200k_512(oracle, tile_rect):
     lists and ranges bit-exact, image and gradients inside the float bar, bitwise repeatable, linear."""
     _full_size_case(oracle, "avatar 200k/512x512", 200000, 512, 512, 0.0, tile_rect, min_pairs=300000,
                     extra_properties=True, layout="body")
-
-
-class _CallCounter(object):
-    """Stands in for the loaded C library and counts the calls per entry point (which backward did the step take?)."""
-
-    def __init__(self, lib):
-        import collections
-        self._lib, self.calls = lib, collections.Counter()
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def counted(*a):
-            self.calls[name] += 1
-            return fn(*a)
-        return counted
 
 
 class _ConvertedCloud(object):
