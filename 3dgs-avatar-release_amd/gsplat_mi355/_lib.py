@@ -35,30 +35,8 @@ class GsGrads(ctypes.Structure):
                                         "dL_dscales", "dL_drotations", "dL_dcov3D")]
 
 
-EXPORTS = ["gs_geom_bytes", "gs_image_bytes", "gs_binning_bytes", "gs_backward_scratch_bytes",
-           "gs_forward_preprocess", "gs_forward_render", "gs_forward", "gs_forward_shared", "gs_backward", "gs_mark_visible", "knn_workspace_bytes",
-           "knn_dist2", "gs_geom_field", "gs_binning_field", "gs_image_field", "gs_status_string",
-           "gs_last_hip_error", "gs_last_stage", "gs_build_info", "gs_profile_enable", "gs_profile_filter", "gs_profile_collect",
-           "gs_l1_loss_workspace_bytes", "gs_l1_loss", "gs_bce_loss", "gs_ssim_workspace_bytes", "gs_ssim_forward", "gs_ssim_backward",
-           "gs_build_covariance", "gs_build_covariance_backward", "gs_sh2rgb", "gs_sh2rgb_backward", "knn_points", "gs_densify_stats", "gs_adam_step",
-           "gs_opacity_image", "gs_backward_with_opacity", "gs_tuning", "gs_profile_reserve", "gs_image_bytes_for", "gs_backward_with_second", "gs_clock_probe", "gs_pair_stats", "gs_xcc_probe",
-           "gs_densify_workspace_bytes", "gs_densify_plan", "gs_densify_apply", "gs_reset_opacity",
-           "gs_aiap_workspace_bytes", "gs_aiap_forward", "gs_aiap_backward",
-           "gs_hashgrid_levels", "gs_hashgrid_workspace_bytes", "gs_hashgrid_forward", "gs_hashgrid_backward",
-           "gs_skin_weights_forward", "gs_skin_weights_backward", "gs_skinning_workspace_bytes", "gs_skinning_forward",
-           "gs_skinning_backward",
-           "gs_mesh_sample", "gs_skin_loss_workspace_bytes", "gs_skin_loss_forward", "gs_skin_loss_backward",
-           "gs_pose_workspace_bytes", "gs_pose_forward", "gs_pose_backward",
-           "gs_pose_encoder_grad_floats", "gs_pose_encoder_forward", "gs_pose_encoder_backward",
-           "gs_nonrigid_workspace_bytes", "gs_nonrigid_apply_forward", "gs_nonrigid_apply_backward",
-           "gs_texture_workspace_bytes", "gs_texture_input_forward", "gs_texture_input_backward",
-           "gs_mlp_workspace_bytes", "gs_mlp_forward", "gs_mlp_backward",
-           "gs_lpips_packed_bytes", "gs_lpips_pack_weights", "gs_lpips_workspace_bytes", "gs_lpips_forward", "gs_lpips_backward",
-           "gs_lpips_conv", "gs_lpips_pool",
-           "gs_grad_norm_workspace_bytes", "gs_grad_norm", "gs_grad_scale", "gs_adam_step_ex"]
-
-GS_E_WORKSPACE = -5  # include/gsplat_mi355.h
-GS_E_CAPTURE = -6
+# status codes (include/gsplat_mi355.h)
+GS_OK, GS_E_BAD_ARG, GS_E_EXCLUSIVE, GS_E_TOO_LARGE, GS_E_HIP, GS_E_WORKSPACE, GS_E_CAPTURE = 0, -1, -2, -3, -4, -5, -6
 GS_ADAM_MAX_TENSORS = 16
 # `field` of gs_geom_field / gs_binning_field / gs_image_field (include/gsplat_mi355.h: GsGeomField, GsBinningField, GsImageField)
 GS_GEOM_DEPTHS, GS_GEOM_TILES, GS_GEOM_REC, GS_GEOM_CLAMPED, GS_GEOM_SORTED_IDX, GS_GEOM_COUNT, GS_GEOM_FIELDS = range(7)
@@ -174,6 +152,133 @@ class GsHashGrid(ctypes.Structure):  # include/gsplat_mi355.h: GsHashGrid
                 ("base_resolution", c_int32), ("per_level_scale", c_float)]
 
 
+_fwd, _grads, _size_out = POINTER(GsFwdArgs), POINTER(GsGrads), POINTER(c_size_t)
+# the forward's three states (geom, binning, image), each with its size, as gs_forward_render and every backward take them
+_states = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+_bwd_head = [_fwd, c_void_p] + _states + [c_int64, c_void_p, c_void_p]  # a, radii, states, num_rendered, out_color, dL_dpix
+_bwd_tail = [c_void_p, c_size_t, _grads, c_void_p]                        # scratch, scratch_bytes, grads, stream
+
+# Every function of include/gsplat_mi355.h, in the header's order: name -> (restype, argtypes).  This is the one place that
+# names them; load() applies it, and tests/test_cabi_host.py holds it (with the structs and constants above) against the
+# header, argument for argument.
+SIGNATURES = {
+    # ---- state-buffer sizes
+    "gs_geom_bytes": (c_int, [c_int32, _size_out]),
+    "gs_image_bytes": (c_int, [c_int32, c_int32, _size_out]),
+    "gs_binning_bytes": (c_int, [c_int64, c_int32, c_int32, _size_out]),
+    "gs_backward_scratch_bytes": (c_int, [c_int64, c_int32, c_int32, c_int32, _size_out]),
+    # ---- forward and backward
+    "gs_forward_preprocess": (c_int, [_fwd, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "gs_forward_render": (c_int, [_fwd] + _states + [c_int64, c_void_p, c_void_p]),
+    "gs_forward": (c_int, [_fwd, c_void_p, c_size_t, c_void_p, c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                           c_void_p, POINTER(c_int64), c_void_p]),
+    "gs_forward_shared": (c_int, [_fwd, c_void_p, c_void_p] + _states + [c_int64, c_void_p, c_void_p]),
+    "gs_backward": (c_int, _bwd_head + _bwd_tail),
+    "gs_opacity_image": (c_int, [_fwd, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gs_backward_with_opacity": (c_int, _bwd_head + [c_void_p] + _bwd_tail),
+    "gs_backward_with_second": (c_int, _bwd_head + [POINTER(GsSecondImage)] + _bwd_tail),
+    "gs_mark_visible": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ---- distCUDA2
+    "knn_workspace_bytes": (c_int, [c_int32, _size_out]),
+    "knn_dist2": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- pre-rasterizer per-Gaussian chains
+    "gs_build_covariance": (c_int, [c_int32, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_void_p]),
+    "gs_build_covariance_backward": (c_int, [c_int32, c_void_p, c_float, c_void_p, c_int32] + [c_void_p] * 4),
+    "gs_sh2rgb": (c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 8),
+    "gs_sh2rgb_backward": (c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 10),
+    # ---- image-side losses
+    "gs_l1_loss_workspace_bytes": (c_int, [c_int64, _size_out]),
+    "gs_l1_loss": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gs_bce_loss": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gs_ssim_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, _size_out]),
+    "gs_ssim_forward": (c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "gs_ssim_backward": (c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 8),
+    # ---- K nearest neighbours
+    "knn_points": (c_int, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- training-step bookkeeping
+    "gs_densify_stats": (c_int, [c_int32] + [c_void_p] * 6),
+    "gs_adam_step": (c_int, [c_int32, POINTER(GsAdamTensor), c_double, c_double, c_double, c_int64, c_void_p]),
+    # ---- the converter's optimizer step
+    "gs_grad_norm_workspace_bytes": (c_int, [c_int32, POINTER(GsGradTensor), _size_out]),
+    "gs_grad_norm": (c_int, [c_int32, POINTER(GsGradTensor), c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gs_grad_scale": (c_int, [c_int32, POINTER(GsGradTensor), c_void_p, c_void_p]),
+    "gs_adam_step_ex": (c_int, [c_int32, POINTER(GsAdamTensorEx), c_double, c_double, c_double, c_int64, c_void_p, c_void_p]),
+    # ---- densification cycle
+    "gs_densify_workspace_bytes": (c_int, [c_int32, _size_out]),
+    "gs_densify_plan": (c_int, [POINTER(GsDensifyPlan), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gs_densify_apply": (c_int, [c_int32, c_int32, c_void_p, c_size_t, c_int32, POINTER(GsDensifyTensor)] + [c_void_p] * 4),
+    "gs_reset_opacity": (c_int, [c_int32] + [c_void_p] * 5),
+    # ---- as-isometric-as-possible regularisers
+    "gs_aiap_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, _size_out]),
+    "gs_aiap_forward": (c_int, [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]),
+    "gs_aiap_backward": (c_int, [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]),
+    # ---- multiresolution hash-grid encoding
+    "gs_hashgrid_levels": (c_int, [POINTER(GsHashGrid), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gs_hashgrid_workspace_bytes": (c_int, [POINTER(GsHashGrid), c_int32, _size_out]),
+    "gs_hashgrid_forward": (c_int, [POINTER(GsHashGrid), c_int32] + [c_void_p] * 4),
+    "gs_hashgrid_backward": (c_int, [POINTER(GsHashGrid), c_int32] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    # ---- linear blend skinning
+    "gs_skin_weights_forward": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "gs_skin_weights_backward": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gs_skinning_workspace_bytes": (c_int, [c_int32, _size_out]),
+    "gs_skinning_forward": (c_int, [c_int32, c_int32] + [c_void_p] * 8),
+    "gs_skinning_backward": (c_int, [c_int32, c_int32] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    # ---- the skinning regulariser
+    "gs_mesh_sample": (c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 13),
+    "gs_skin_loss_workspace_bytes": (c_int, [c_int32, _size_out]),
+    "gs_skin_loss_forward": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gs_skin_loss_backward": (c_int, [c_int32, c_int32] + [c_void_p] * 5),
+    # ---- SMPL pose correction
+    "gs_pose_workspace_bytes": (c_int, [c_int32, _size_out]),
+    "gs_pose_forward": (c_int, [POINTER(GsPoseArgs)] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "gs_pose_backward": (c_int, [POINTER(GsPoseArgs)] + [c_void_p] * 11),
+    # ---- the non-rigid deformer around its MLP
+    "gs_pose_encoder_grad_floats": (c_int, [c_int32, _size_out]),
+    "gs_pose_encoder_forward": (c_int, [POINTER(GsPoseEncArgs), c_void_p, c_void_p, c_void_p]),
+    "gs_pose_encoder_backward": (c_int, [POINTER(GsPoseEncArgs)] + [c_void_p] * 6),
+    "gs_nonrigid_workspace_bytes": (c_int, [c_int32, c_int32, _size_out]),
+    "gs_nonrigid_apply_forward": (c_int, [c_int32] * 4 + [c_void_p] * 10 + [c_size_t, c_void_p]),
+    "gs_nonrigid_apply_backward": (c_int, [c_int32] * 4 + [c_void_p] * 14),
+    # ---- the input of the ColorMLP texture
+    "gs_texture_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, _size_out]),
+    "gs_texture_input_forward": (c_int, [POINTER(GsTextureArgs), c_void_p, c_void_p]),
+    "gs_texture_input_backward": (c_int, [POINTER(GsTextureArgs), c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- the dense networks
+    "gs_mlp_workspace_bytes": (c_int, [POINTER(GsMlpArgs), c_int32, _size_out]),
+    "gs_mlp_forward": (c_int, [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gs_mlp_backward": (c_int, [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- the LPIPS-VGG perceptual loss
+    "gs_lpips_packed_bytes": (c_int, [_size_out]),
+    "gs_lpips_pack_weights": (c_int, [POINTER(GsLpipsArgs), c_void_p, c_size_t, c_void_p]),
+    "gs_lpips_workspace_bytes": (c_int, [c_int32] * 5 + [_size_out]),
+    "gs_lpips_forward": (c_int, [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "gs_lpips_backward": (c_int, [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                  c_void_p]),
+    "gs_lpips_conv": (c_int, [c_void_p] + [c_int32] * 5 + [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gs_lpips_pool": (c_int, [c_int32] * 4 + [c_void_p] * 5),
+    # ---- introspection for parity tests
+    "gs_geom_field": (c_int, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),
+    "gs_binning_field": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "gs_image_field": (c_int, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "gs_image_bytes_for": (c_int, [_fwd, _size_out]),
+    # ---- per-stage timing
+    "gs_profile_reserve": (c_int, [c_int]),
+    "gs_profile_enable": (c_int, [c_int]),
+    "gs_profile_filter": (c_int, [c_char_p]),
+    "gs_profile_collect": (c_int, [c_int, POINTER(c_char_p), POINTER(c_float), POINTER(c_int32), POINTER(c_int32)]),
+    # ---- report counters, probes, tuning switches, status
+    "gs_pair_stats": (c_int, [_fwd] + _states + [c_int64, c_void_p, c_void_p]),
+    "gs_clock_probe": (c_int, [c_void_p, c_int32, c_void_p]),
+    "gs_xcc_probe": (c_int, [c_void_p, c_int32, c_void_p]),
+    "gs_tuning": (c_int, [c_char_p, c_int]),
+    "gs_status_string": (c_char_p, [c_int]),
+    "gs_last_hip_error": (c_int, []),
+    "gs_last_stage": (c_char_p, []),
+    "gs_build_info": (c_char_p, []),
+}
+EXPORTS = list(SIGNATURES)
+
 _lock = threading.Lock()
 _lib = None
 
@@ -191,122 +296,9 @@ def load():
             raise RuntimeError("libgsplat_mi355.so not found at %s: build it with "
                                "`python 3dgs-avatar-release_amd/build.py` (there is no CPU fallback)" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        L.gs_geom_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_image_bytes.argtypes = [c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_image_bytes_for.argtypes = [POINTER(GsFwdArgs), POINTER(c_size_t)]
-        L.gs_binning_bytes.argtypes = [c_int64, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_backward_scratch_bytes.argtypes = [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_forward_preprocess.argtypes = [POINTER(GsFwdArgs), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
-                                            c_void_p, c_void_p]
-        L.gs_forward_render.argtypes = [POINTER(GsFwdArgs), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_int64, c_void_p, c_void_p]
-        L.gs_forward.argtypes = [POINTER(GsFwdArgs), c_void_p, c_size_t, c_void_p, c_size_t, c_int64, c_void_p, c_size_t,
-                                 c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]
-        L.gs_forward_shared.argtypes = [POINTER(GsFwdArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p, c_size_t, c_int64, c_void_p, c_void_p]
-        L.gs_backward.argtypes = [POINTER(GsFwdArgs), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
-                                  c_size_t, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(GsGrads), c_void_p]
-        L.gs_opacity_image.argtypes = [POINTER(GsFwdArgs), c_void_p, c_size_t, c_void_p, c_void_p]
-        L.gs_backward_with_opacity.argtypes = [POINTER(GsFwdArgs), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
-                                               c_size_t, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(GsGrads),
-                                               c_void_p]
-        L.gs_backward_with_second.argtypes = [POINTER(GsFwdArgs), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
-                                              c_size_t, c_int64, c_void_p, c_void_p, POINTER(GsSecondImage), c_void_p, c_size_t,
-                                              POINTER(GsGrads), c_void_p]
-        L.gs_mark_visible.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.knn_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.knn_dist2.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_l1_loss_workspace_bytes.argtypes = [c_int64, POINTER(c_size_t)]
-        L.gs_l1_loss.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_bce_loss.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_ssim_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_ssim_forward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_size_t, c_void_p]
-        L.gs_ssim_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p]
-        L.gs_build_covariance.argtypes = [c_int32, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_void_p]
-        L.gs_build_covariance_backward.argtypes = [c_int32, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
-                                                   c_void_p]
-        L.gs_sh2rgb.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p]
-        L.gs_sh2rgb_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p]
-        L.knn_points.argtypes = [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_densify_stats.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_adam_step.argtypes = [c_int32, POINTER(GsAdamTensor), c_double, c_double, c_double, c_int64, c_void_p]
-        L.gs_grad_norm_workspace_bytes.argtypes = [c_int32, POINTER(GsGradTensor), POINTER(c_size_t)]
-        L.gs_grad_norm.argtypes = [c_int32, POINTER(GsGradTensor), c_float, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_grad_scale.argtypes = [c_int32, POINTER(GsGradTensor), c_void_p, c_void_p]
-        L.gs_adam_step_ex.argtypes = [c_int32, POINTER(GsAdamTensorEx), c_double, c_double, c_double, c_int64, c_void_p,
-                                      c_void_p]
-        L.gs_densify_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_densify_plan.argtypes = [POINTER(GsDensifyPlan), c_void_p, c_size_t, c_void_p, c_void_p]
-        L.gs_densify_apply.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, POINTER(GsDensifyTensor), c_void_p,
-                                       c_void_p, c_void_p, c_void_p]
-        L.gs_reset_opacity.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_aiap_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_aiap_forward.argtypes = [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]
-        L.gs_aiap_backward.argtypes = [c_int32, c_int32, c_void_p, c_int32, POINTER(GsAiapSet), c_void_p, c_size_t, c_void_p]
-        L.gs_hashgrid_levels.argtypes = [POINTER(GsHashGrid), c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_hashgrid_workspace_bytes.argtypes = [POINTER(GsHashGrid), c_int32, POINTER(c_size_t)]
-        L.gs_hashgrid_forward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_hashgrid_backward.argtypes = [POINTER(GsHashGrid), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_size_t, c_void_p]
-        L.gs_skin_weights_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-        L.gs_skin_weights_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_skinning_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_skinning_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p]
-        L.gs_skinning_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_mesh_sample.argtypes = [c_int32, c_int32, c_int32] + [c_void_p] * 13
-        L.gs_skin_loss_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_skin_loss_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_skin_loss_backward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_pose_workspace_bytes.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_pose_forward.argtypes = [POINTER(GsPoseArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                      c_void_p]
-        L.gs_pose_backward.argtypes = [POINTER(GsPoseArgs)] + [c_void_p] * 11
-        L.gs_pose_encoder_grad_floats.argtypes = [c_int32, POINTER(c_size_t)]
-        L.gs_pose_encoder_forward.argtypes = [POINTER(GsPoseEncArgs), c_void_p, c_void_p, c_void_p]
-        L.gs_pose_encoder_backward.argtypes = [POINTER(GsPoseEncArgs)] + [c_void_p] * 6
-        L.gs_nonrigid_workspace_bytes.argtypes = [c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_nonrigid_apply_forward.argtypes = [c_int32] * 4 + [c_void_p] * 10 + [c_size_t, c_void_p]
-        L.gs_nonrigid_apply_backward.argtypes = [c_int32] * 4 + [c_void_p] * 14
-        L.gs_texture_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_texture_input_forward.argtypes = [POINTER(GsTextureArgs), c_void_p, c_void_p]
-        L.gs_texture_input_backward.argtypes = [POINTER(GsTextureArgs), c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p,
-                                                c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_mlp_workspace_bytes.argtypes = [POINTER(GsMlpArgs), c_int32, POINTER(c_size_t)]
-        L.gs_mlp_forward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_mlp_backward.argtypes = [POINTER(GsMlpArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        L.gs_lpips_packed_bytes.argtypes = [POINTER(c_size_t)]
-        L.gs_lpips_pack_weights.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_size_t, c_void_p]
-        L.gs_lpips_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
-        L.gs_lpips_forward.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
-        L.gs_lpips_backward.argtypes = [POINTER(GsLpipsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p]
-        L.gs_lpips_conv.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p,
-                                    c_void_p, c_void_p]
-        L.gs_lpips_pool.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.gs_geom_field.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
-        L.gs_binning_field.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(c_void_p)]
-        L.gs_image_field.argtypes = [c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]
-        L.gs_clock_probe.argtypes = [c_void_p, c_int32, c_void_p]
-        L.gs_xcc_probe.argtypes = [c_void_p, c_int32, c_void_p]
-        L.gs_pair_stats.argtypes = [POINTER(GsFwdArgs), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_int64, c_void_p,
-                                    c_void_p]
-        L.gs_tuning.argtypes = [c_char_p, c_int]
-        L.gs_profile_reserve.argtypes = [c_int]
-        L.gs_profile_enable.argtypes = [c_int]
-        L.gs_profile_filter.argtypes = [c_char_p]
-        L.gs_profile_collect.argtypes = [c_int, POINTER(c_char_p), POINTER(c_float), POINTER(c_int32), POINTER(c_int32)]
-        for name in EXPORTS:
-            getattr(L, name).restype = c_int
-        L.gs_status_string.restype = c_char_p
-        L.gs_status_string.argtypes = [c_int]
-        L.gs_last_stage.restype = c_char_p
-        L.gs_build_info.restype = c_char_p
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -315,7 +307,7 @@ def check(rc):
     if rc != 0:
         L = load()
         msg = L.gs_status_string(rc).decode()
-        if rc == -4:
+        if rc == GS_E_HIP:
             msg += " %d in stage '%s'" % (L.gs_last_hip_error(), L.gs_last_stage().decode())
         raise RuntimeError("gsplat_mi355: " + msg)
 

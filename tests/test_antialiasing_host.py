@@ -6,12 +6,12 @@ own forward, which is what fixes their signs and the factor on b."""
 import ctypes
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import antialias_ref as ref
 import helpers
 
@@ -40,16 +40,8 @@ def test_struct_field_is_last_in_binding_and_header_and_fills_tail_padding():
     from gsplat_mi355 import _lib
     assert _lib.GsFwdArgs._fields_[-1] == ("antialiasing", ctypes.c_int32)
     assert _lib.GsFwdArgs._fields_[-2] == ("forward_only", ctypes.c_int32)
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
-    body = header[header.index("typedef struct GsFwdArgs {"):header.index("} GsFwdArgs;")]
-    fields = []
-    for decl in re.sub(r"/\*.*?\*/", "", body.split("{", 1)[1], flags=re.S).split(";"):  # (the comments hold semicolons)
-        decl = decl.strip()
-        if decl:
-            names = re.sub(r"^(const\s+)?(float|int32_t|int64_t)\s*", "", decl)
-            fields += [n.strip(" *") for n in names.split(",")]
-    assert fields == [f[0] for f in _lib.GsFwdArgs._fields_]
-    assert fields[-1] == "antialiasing"
+    header = abi_header.text()
+    assert [f.name for f in abi_header.parse().structs["GsFwdArgs"][-2:]] == ["forward_only", "antialiasing"]
     size = ctypes.sizeof(_lib.GsFwdArgs)
     assert size % 8 == 0
     # the field sits right behind forward_only, in what was tail padding: no earlier offset and not the size changed

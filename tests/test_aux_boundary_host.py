@@ -16,6 +16,8 @@ import re
 import pytest
 import torch
 
+import abi_header
+
 pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason="fake device pointers: host logic only, pinned without a device")
 
 FAKE = 0x100000   # non-null, 16-byte aligned, never dereferenced
@@ -476,11 +478,7 @@ RECORDED = {
 
 @pytest.fixture(scope="module")
 def lib():
-    from gsplat_mi355 import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
+    return abi_header.lib()
 
 
 def test_every_entry_point_outside_the_frame_path_is_pinned(lib):

@@ -1,34 +1,192 @@
-"""C-ABI library on the CPU (no GPU needed): it loads, exports every symbol include/gsplat_mi355.h declares,
-its size functions and argument validation run without touching a device."""
+"""C-ABI library on the CPU (no GPU needed): the binding gsplat_mi355/_lib.py states what include/gsplat_mi355.h declares --
+every function's arguments, every struct's fields and layout, every constant -- the library loads and exports all of it,
+and its size functions and argument validation run without touching a device."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
+
+import abi_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from gsplat_mi355 import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("gsplat_build", os.path.join(ROOT, "3dgs-avatar-release_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    return _lib
+    return abi_header.lib()
 
 
-def test_every_declared_symbol_is_exported(lib):
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
-    declared = set(re.findall(r"^(?:int|const char\*)\s+((?:gs|knn)_[a-z0-9_]+)\s*\(", header, flags=re.M))
-    assert len(declared) >= 18
-    L = lib.load()
-    for name in declared:
-        assert hasattr(L, name), name
-    assert declared == set(lib.EXPORTS)
+@pytest.fixture(scope="module")
+def header():
+    return abi_header.parse()
+
+
+# ---- the binding (gsplat_mi355/_lib.py: SIGNATURES, the Structure classes, the GS_* constants) against the header, whole
+_INT_CODES = {"b": True, "h": True, "i": True, "l": True, "q": True, "B": False, "H": False, "I": False, "L": False, "Q": False}
+C_SCALARS = {  # what the header's scalar types are on the one ABI the library is built for (LP64): (kind, bytes, signed)
+    "int32_t": ("int", 4, True), "int64_t": ("int", 8, True), "uint8_t": ("int", 1, False), "uint32_t": ("int", 4, False),
+    "uint64_t": ("int", 8, False), "size_t": ("int", 8, False), "int": ("int", 4, True), "float": ("float", 4, None),
+    "double": ("float", 8, None), "char": ("int", 1, True)}
+
+
+def _scalar(ct):
+    """(kind, bytes, signed) of a ctypes scalar, None for anything else (pointers, c_void_p and c_char_p included)."""
+    code = getattr(ct, "_type_", None) if isinstance(ct, type) and issubclass(ct, ctypes._SimpleCData) else None
+    if code in ("f", "d"):
+        return ("float", ctypes.sizeof(ct), None)
+    if code in _INT_CODES:
+        return ("int", ctypes.sizeof(ct), _INT_CODES[code])
+    return None
+
+
+def abi_mismatch(ct, t, length=None):
+    """None when the ctypes type `ct` is ABI-equivalent to the header's type `t` (an array of `length` of them when that is
+    not None), else what differs."""
+    if length is not None or (isinstance(ct, type) and issubclass(ct, ctypes.Array)):
+        if not (isinstance(ct, type) and issubclass(ct, ctypes.Array)) or length is None:
+            return "array in one, not in the other"
+        if ct._length_ != length:
+            return "%d elements, the header has %d" % (ct._length_, length)
+        return abi_mismatch(ct._type_, t)
+    if t.depth == 0:
+        if t.base not in C_SCALARS:
+            return "a %s by value" % t.base
+        if _scalar(ct) == C_SCALARS[t.base]:
+            return None
+        return "%s is %r, %s is %r" % (getattr(ct, "__name__", ct), _scalar(ct), t.base, C_SCALARS[t.base])
+    is_pointer = isinstance(ct, type) and issubclass(ct, ctypes._Pointer)
+    if t.depth == 2:
+        want = ctypes.c_char_p if (t.base, t.const) == ("char", True) else ctypes.c_void_p
+        return None if is_pointer and ct._type_ is want else "pointer to pointer: POINTER(%s) expected" % want.__name__
+    if t.depth != 1:
+        return "pointer depth %d" % t.depth
+    if ct is ctypes.c_char_p:
+        return None if (t.base, t.const) == ("char", True) else "c_char_p for %s*" % t.base
+    if t.base not in C_SCALARS and t.base != "void":  # a struct: by POINTER of the class of that name, never a bare c_void_p
+        ok = is_pointer and issubclass(ct._type_, ctypes.Structure) and ct._type_.__name__ == t.base
+        return None if ok else "POINTER(%s) expected" % t.base
+    if ct is ctypes.c_void_p:
+        return None
+    if not is_pointer:
+        return "%s for a pointer" % getattr(ct, "__name__", ct)
+    if t.base == "void" or _scalar(ct._type_) is None:
+        return "POINTER(%s) for %s*" % (ct._type_.__name__, t.base)
+    return None if _scalar(ct._type_)[:2] == C_SCALARS[t.base][:2] else "pointee %r, the header's is %r" % (
+        _scalar(ct._type_), C_SCALARS[t.base])
+
+
+def _structures(lib):
+    return {n: c for n, c in vars(lib).items()
+            if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == lib.__name__}
+
+
+def test_the_scalar_table_is_this_platform_s():
+    for name, ct in (("int32_t", ctypes.c_int32), ("int64_t", ctypes.c_int64), ("uint8_t", ctypes.c_uint8),
+                     ("uint32_t", ctypes.c_uint32), ("uint64_t", ctypes.c_uint64), ("size_t", ctypes.c_size_t), ("int", ctypes.c_int),
+                     ("float", ctypes.c_float), ("double", ctypes.c_double), ("char", ctypes.c_byte)):
+        assert _scalar(ct) == C_SCALARS[name], name
+    assert set(C_SCALARS) == set(abi_header.SCALARS)
+    assert _scalar(ctypes.c_void_p) is None and _scalar(ctypes.c_char_p) is None
+
+
+def test_every_function_is_bound_as_the_header_declares_it(lib, header):
+    raw = abi_header.text()
+    declared = re.findall(r"^(?:int|const char\*)\s+((?:gs|knn)_\w+)\s*\(", raw, flags=re.M)  # an independent line count
+    assert len(declared) == len(set(declared)) == len(header.functions) >= 90
+    assert set(declared) == set(header.functions)
+    assert set(lib.SIGNATURES) == set(header.functions)
+    assert lib.EXPORTS == list(lib.SIGNATURES) == list(header.functions)  # (the header's order)
+    wrong = []
+    for name, fn in header.functions.items():
+        restype, argtypes = lib.SIGNATURES[name]
+        want = {("int", False, 0): ctypes.c_int, ("char", True, 1): ctypes.c_char_p}[tuple(fn.restype)]
+        if restype is not want:
+            wrong.append("%s: restype %s" % (name, restype))
+        if len(argtypes) != len(fn.params):
+            wrong.append("%s: %d arguments bound, %d declared" % (name, len(argtypes), len(fn.params)))
+            continue
+        for ct, (pname, t) in zip(argtypes, fn.params):
+            why = abi_mismatch(ct, t)
+            if why:
+                wrong.append("%s(%s): %s" % (name, pname, why))
+    assert wrong == []
+    L = lib.load()  # load() applies the table: every symbol is there, with the table's types
+    for name, (restype, argtypes) in lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_every_struct_is_bound_as_the_header_declares_it(lib, header):
+    classes = _structures(lib)
+    assert len(header.structs) == abi_header.text().count("typedef struct") >= 15
+    assert set(classes) == set(header.structs)
+    wrong = []
+    for name, fields in header.structs.items():
+        bound = classes[name]._fields_
+        if [f[0] for f in bound] != [f.name for f in fields]:
+            wrong.append("%s: fields %s, the header has %s" % (name, [f[0] for f in bound], [f.name for f in fields]))
+            continue
+        for (fname, ct), f in zip(bound, fields):
+            why = abi_mismatch(ct, f.type, f.length)
+            if why:
+                wrong.append("%s.%s: %s" % (name, fname, why))
+    assert wrong == []
+
+
+CONSTANTS_NOT_IN_THE_HEADER = {"GS_COUNT_NOT_ONES"}  # mirrors csrc/common.h: tests/test_invdepth_host.py holds it
+
+
+def test_every_constant_of_the_binding_is_the_header_s(lib, header):
+    bound = {n: v for n, v in vars(lib).items() if n.startswith("GS_") and isinstance(v, int)}
+    assert CONSTANTS_NOT_IN_THE_HEADER <= set(bound)
+    wrong = {n: (v, header.constants.get(n)) for n, v in bound.items()
+             if n not in CONSTANTS_NOT_IN_THE_HEADER and header.constants.get(n) != v}
+    assert wrong == {}
+    for n in ("GS_OK", "GS_E_BAD_ARG", "GS_E_EXCLUSIVE", "GS_E_TOO_LARGE", "GS_E_HIP", "GS_E_WORKSPACE", "GS_E_CAPTURE"):
+        assert n in bound, n
+    # the field numbers of the introspection calls are ABI: all of the header's enums are bound, at these values
+    fields = [n for n in header.constants if re.match(r"GS_(GEOM|BIN|IMG)_", n)]
+    assert len(fields) == 6 + 2 + 10 + 3 and set(fields) <= set(bound)  # fields + the three counts
+    assert (lib.GS_GEOM_FIELDS, lib.GS_BIN_FIELDS, lib.GS_IMG_FIELDS) == (6, 2, 10)
+    assert (lib.GS_GEOM_COUNT, lib.GS_IMG_ORDER, lib.GS_IMG_CW_REC) == (5, 5, 9)
+    assert (lib.GS_OK, lib.GS_E_BAD_ARG, lib.GS_E_EXCLUSIVE, lib.GS_E_TOO_LARGE, lib.GS_E_HIP) == (0, -1, -2, -3, -4)
+
+
+def test_struct_layouts_are_the_compiler_s(lib, header, tmp_path):
+    """The reader and ctypes could share a wrong idea of padding: a host program that includes the header prints sizeof of
+    every struct and offsetof of every field, and ctypes must say the same."""
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "gsplat_mi355.h"', "int main() {"]
+    for name, fields in header.structs.items():
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        for f in fields:
+            lines.append('    printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (name, f.name, name, f.name))
+    lines += ["    return 0;", "}", ""]
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    cc = abi_header.build_module().hipcc()
+    r = subprocess.run([cc, "-x", "c++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    got = {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
+    want = {}
+    for name, cls in _structures(lib).items():
+        want[name] = ctypes.sizeof(cls)
+        for fname, _ in cls._fields_:
+            want["%s.%s" % (name, fname)] = getattr(cls, fname).offset
+    assert got == want
+    assert (got["GsFwdArgs"], got["GsFwdArgs.antialiasing"]) == (184, 180)
+
+
+def test_the_integration_guide_shows_the_binding_s_frame_arguments(lib):
+    """INTEGRATION.md's GsFwdArgs snippet: the same ("name", c_type) pairs in the same order as the binding's."""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    start = doc.index("class GsFwdArgs(ctypes.Structure)")
+    snippet = doc[start:doc.index("\n\n", start)]
+    pairs = re.findall(r'\("(\w+)",\s*(c_\w+)\)', snippet)
+    assert [(n, getattr(ctypes, t)) for n, t in pairs] == list(lib.GsFwdArgs._fields_)
 
 
 def test_size_functions_and_status_strings(lib):
@@ -424,13 +582,3 @@ def test_introspection_fields_sit_where_they_did(lib):
     assert L.gs_binning_field(FAKE, -1, 64, 64, 0, ctypes.byref(out)) == BAD_ARG
     assert L.gs_image_field(FAKE, 64, 64, 0, None) == BAD_ARG
 
-
-def test_field_names_of_the_binding_are_the_header_s(lib):
-    """The GS_GEOM_* / GS_BIN_* / GS_IMG_* constants of _lib.py mirror the enums of include/gsplat_mi355.h."""
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
-    names = re.findall(r"\b(GS_(?:GEOM|BIN|IMG)_[A-Z0-9_]+)\s*=\s*(\d+)", header)
-    assert len(names) == 6 + 2 + 10 + 3  # fields + the three counts
-    for name, value in names:
-        assert getattr(lib, name) == int(value), name
-    assert (lib.GS_GEOM_FIELDS, lib.GS_BIN_FIELDS, lib.GS_IMG_FIELDS) == (6, 2, 10)
-    assert (lib.GS_GEOM_COUNT, lib.GS_IMG_ORDER, lib.GS_IMG_CW_REC) == (5, 5, 9)

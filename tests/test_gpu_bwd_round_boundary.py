@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,10 +42,7 @@ def _backward_code_object():
         import __graft_entry__
         __graft_entry__.build()
         if not os.path.exists(obj):  # (the library was up to date, the objects are gone)
-            spec = importlib.util.spec_from_file_location("gsplat_build", os.path.join(PKG, "build.py"))
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-            mod.build(force=True)
+            abi_header.build_module().build(force=True)
     spec = importlib.util.spec_from_file_location("check_inflight", os.path.join(PKG, "check_inflight.py"))
     ci = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ci)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import helpers
 import test_cabi_host as cabi
 from test_cabi_host import lib  # noqa: F401  (the fixture: builds the library if it is not there)
@@ -23,18 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_second_image_struct_has_the_trailing_field_in_binding_and_header():
     from gsplat_mi355 import _lib
     assert _lib.GsSecondImage._fields_[-1] == ("dL_dcolors", ctypes.c_void_p)
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
-    body = header[header.index("typedef struct GsSecondImage {"):header.index("} GsSecondImage;")]
-    fields = []
-    for decl in re.sub(r"/\*.*?\*/", "", body.split("{", 1)[1], flags=re.S).split(";"):
-        decl = decl.strip()
-        if decl:
-            fields.append(re.sub(r"^(const\s+)?(float|void|size_t|int32_t)\s*", "", decl).strip(" *"))
-    assert fields == [n for n, _ in _lib.GsSecondImage._fields_]
-    # pointer fields are pointers in the header, the others are not
-    for name, ctype in _lib.GsSecondImage._fields_:
-        decl = re.search(r"([^;{]*\b%s);" % name, re.sub(r"/\*.*?\*/", "", body, flags=re.S)).group(1)
-        assert ("*" in decl) == (ctype is ctypes.c_void_p), decl
+    assert abi_header.parse().structs["GsSecondImage"][-1].name == "dL_dcolors"
+    header = abi_header.text()
     assert "get theirs when asked" in header and "get none" not in header
     capture = header[header.index("Stream capture"):header.index("typedef struct GsFwdArgs {")]
     assert "GsSecondImage.dL_dcolors" in capture

