@@ -17,14 +17,13 @@
 //   The arithmetic is compiled with -ffp-contract=off (build.py STRICT): xd == xc bit for bit gives a_p == b_p exactly.
 //
 // Passes (forward):
-//   aiap_fwd        one thread per source row: its K-1 pairs' |a - b| for every set, per-block partial sums (fixed
-//                   order: thread, DPP ladder, waves in order), per-block counts of idx values outside [0, N) (never
+//   aiap_fwd        one thread per source row: its K-1 pairs' |a - b| for every set, per-block partial sums (block_sum,
+//                   waves pairwise: ordered_sum.h), per-block counts of idx values outside [0, N) (never
 //                   dereferenced: such a pair adds nothing), and the (target, source) keys of the adjacency sort
 //                   (target N for a bad index, so those sort last and fall outside every list).  It also clears the
 //                   sort's digit totals, so the call needs no memset node.
 //   radix sort      radix_sort.hip, stable LSD on the target: pairs of one target stay in (i, k) order.
-//   aiap_offsets    start[t] = the first sorted pair whose target is >= t, t = 0 .. N (every word written exactly once:
-//                   by the pair that ends the gap in front of it; gaps longer than a wave are filled by the whole wave);
+//   aiap_offsets    start[t] = the first sorted pair whose target is >= t, t = 0 .. N (list_starts: sorted_lists.h);
 //                   its last n_sets + 1 workgroups add the loss partials (in double, fixed order) and the bad counts.
 // Backward: one thread per row writes every output row exactly once: its outgoing pairs, then its incoming pairs in
 // adjacency order.  A row with more than AIAP_HEAVY incoming pairs (a hub) is taken over by its whole wave: lane l adds
@@ -32,11 +31,12 @@
 // Rows are read with 4-byte loads (a D = 3 row is 12 bytes: any 4-byte-aligned base is accepted).
 #include "common.h"
 #include "boundary.h"
+#include "ordered_sum.h"
+#include "sorted_lists.h"
 
 #define AIAP_THREADS 256
 #define AIAP_HEAVY 64  // incoming pairs above which the wave takes a row over
 
-static inline size_t aiap_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int aiap_blocks(int n) { return (n + AIAP_THREADS - 1) / AIAP_THREADS; }
 static inline int aiap_bits(int N) {  // bits of a key in [0, N]
     int b = 1;
@@ -45,36 +45,28 @@ static inline int aiap_bits(int N) {  // bits of a key in [0, N]
 }
 
 // workspace: misc u32[4] (word 0: bad index count) | partial f32[2][fwd blocks] | bad partial u32[fwd blocks] |
-// keys / values u32[2][2][M] (the sort's ping-pong buffers) | sort tables | start u32[N + 1]
+// the pair sort's buffers and tables for M pairs (PairSort) | start u32[N + 1]
 struct AiapWs {
     uint32_t* misc;
     float* partial;
     uint32_t* badp;
-    uint32_t *k0, *v0, *k1, *v1;
-    uint32_t* hist;
+    PairSort sort;
     uint32_t* start;
+    size_t total;
 };
-static inline size_t aiap_carve(int N, int K, char* base, AiapWs* w) {
+static inline AiapWs aiap_carve(int N, int K, void* base) {
     const size_t M = (size_t)N * (size_t)(K - 1), nb = (size_t)aiap_blocks(N);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += aiap_align(bytes); return p; };
-    char* misc = take(16);
-    char* partial = take(2 * nb * 4);
-    char* badp = take(nb * 4);
-    char* k0 = take(M * 4);
-    char* v0 = take(M * 4);
-    char* k1 = take(M * 4);
-    char* v1 = take(M * 4);
-    char* hist = take(sort_table_words(M) * 4);
-    char* start = take(((size_t)N + 1) * 4);
-    if (w) {
-        w->misc = (uint32_t*)misc; w->partial = (float*)partial; w->badp = (uint32_t*)badp;
-        w->k0 = (uint32_t*)k0; w->v0 = (uint32_t*)v0; w->k1 = (uint32_t*)k1; w->v1 = (uint32_t*)v1;
-        w->hist = (uint32_t*)hist; w->start = (uint32_t*)start;
-    }
-    return o;
+    Carver c(base);
+    AiapWs w;
+    w.misc = c.take<uint32_t>(4);
+    w.partial = c.take<float>(2 * nb);
+    w.badp = c.take<uint32_t>(nb);
+    w.sort = PairSort::carve(c, M);
+    w.start = c.take<uint32_t>((size_t)N + 1);
+    w.total = c.o;
+    return w;
 }
-static size_t aiap_workspace_bytes(int N, int K) { return aiap_carve(N, K, nullptr, nullptr); }
+static size_t aiap_workspace_bytes(int N, int K) { return aiap_carve(N, K, nullptr).total; }
 
 struct AiapSet {
     const float* xc;
@@ -128,22 +120,13 @@ __device__ __forceinline__ float aiap_row_loss(const AiapSet& S, uint32_t i, con
     return acc;
 }
 
-// block sum of one float per thread, fixed order (DPP ladder, then the four waves in order); valid in thread 0
-__device__ __forceinline__ float aiap_block_sum(float v, float* lds /* 4 */) {
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    v = wave_sum(v);
-    if (lane == 0) lds[wv] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
 template <int D0, int D1>
 __global__ __launch_bounds__(AIAP_THREADS) void aiap_fwd_kernel(int N, int K, const long long* __restrict__ idx, AiapSet s0,
                                                                AiapSet s1, AiapWs w, ZeroJob zj) {
     __shared__ float lds[2][AIAP_THREADS / WAVE];
     __shared__ uint32_t ldsb[AIAP_THREADS / WAVE];
     const uint32_t i = blockIdx.x * AIAP_THREADS + threadIdx.x;
-    for (int z = blockIdx.x * AIAP_THREADS + threadIdx.x; z < zj.words; z += gridDim.x * AIAP_THREADS) zj.ptr[z] = 0u;
+    zero_job(zj);
     float l0 = 0.0f, l1 = 0.0f;
     uint32_t bad = 0;
     if (i < (uint32_t)N) {
@@ -157,14 +140,14 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_fwd_kernel(int N, int K, co
             js[k] = ok ? (uint32_t)j : 0xFFFFFFFFu;
             bad += ok ? 0u : 1u;
             const size_t p = (size_t)i * nk + k;
-            w.k0[p] = ok ? (uint32_t)j : (uint32_t)N;
-            w.v0[p] = i;
+            w.sort.k0[p] = ok ? (uint32_t)j : (uint32_t)N;  // (a bad index: key N, behind every list)
+            w.sort.v0[p] = i;
         }
         l0 = aiap_row_loss<D0>(s0, i, js, nk);
         l1 = aiap_row_loss<D1>(s1, i, js, nk);
     }
-    const float t0 = aiap_block_sum(l0, lds[0]);
-    const float t1 = D1 ? aiap_block_sum(l1, lds[1]) : 0.0f;
+    const float t0 = block_sum<AIAP_THREADS, WavesPairwise>(l0, lds[0]);
+    const float t1 = D1 ? block_sum<AIAP_THREADS, WavesPairwise>(l1, lds[1]) : 0.0f;
     const uint32_t wb = wave_sum(bad);
     if ((threadIdx.x & (WAVE - 1)) == 0) ldsb[threadIdx.x / WAVE] = wb;
     __syncthreads();
@@ -181,7 +164,6 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_offsets_kernel(int N, long 
                                                                    int n_sets, const float* __restrict__ partial,
                                                                    const uint32_t* __restrict__ badp, uint32_t* misc,
                                                                    float* loss0, float* loss1) {
-    const int lane = threadIdx.x & (WAVE - 1);
     if ((int)blockIdx.x >= nb_off) {
         // loss of set `s` (or, past them, the bad-index count): thread t adds partials t, t + 256, ... in order (double)
         __shared__ double ld[AIAP_THREADS];
@@ -203,34 +185,15 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_offsets_kernel(int N, long 
         }
         return;
     }
-    const long long q = (long long)blockIdx.x * AIAP_THREADS + threadIdx.x;  // q = M: a virtual pair of target N
-    const bool valid = q <= M;
-    long long lo = 0, hi = -1;  // this pair writes start[lo .. hi] = q
-    if (valid) {
-        const long long key = q < M ? (long long)ks[q] : (long long)N;
-        const long long prev = q > 0 ? (long long)ks[q - 1] : -1;
-        lo = prev + 1;
-        hi = key < N ? key : (long long)N;
-    }
-    const bool big = hi - lo + 1 > WAVE;
-    if (!big)
-        for (long long t = lo; t <= hi; t++) start[t] = (uint32_t)q;
-    unsigned long long bal = __ballot(big);
-    while (bal) {  // (wave-uniform)
-        const int L = __ffsll((long long)bal) - 1;
-        bal &= bal - 1;
-        const int blo = __shfl((int)lo, L), bhi = __shfl((int)hi, L), bq = __shfl((int)q, L);
-        for (int t = blo + lane; t <= bhi; t += WAVE) start[t] = (uint32_t)bq;
-    }
+    // (the keys are targets in [0, N] -- aiap_fwd stores a bad index as N -- so no list start needs clamping to N)
+    list_starts(ks, M, (uint32_t)N, (long long)blockIdx.x * AIAP_THREADS + threadIdx.x, start);
 }
 
 static int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, void* workspace, hipStream_t s) {
-    AiapWs w;
-    aiap_carve(N, K, (char*)workspace, &w);
+    const AiapWs w = aiap_carve(N, K, workspace);
     const long long M = (long long)N * (K - 1);
     const int bits = aiap_bits(N), nb = aiap_blocks(N);
-    ZeroJob zj;
-    sort_totals_region(w.hist, M, bits, &zj.ptr, &zj.words);
+    const ZeroJob zj = w.sort.totals_job(M, bits);
     const AiapSet s0 = aiap_set(&sets[0]), s1 = aiap_set(n_sets > 1 ? &sets[1] : nullptr);
     StageScope st("aiap_fwd", s);
 #define AIAP_FWD(A, B) hipLaunchKernelGGL((aiap_fwd_kernel<A, B>), dim3(nb), dim3(AIAP_THREADS), 0, s, N, K, idx, s0, s1, w, zj)
@@ -243,9 +206,9 @@ static int launch_aiap_forward(int N, int K, const long long* idx, int n_sets, c
     else AIAP_FWD(6, 6);
 #undef AIAP_FWD
     GS_LAUNCH_CHECK("aiap_fwd", 0, s);
-    const int rc = launch_sort_pairs(w.k0, w.v0, w.k1, w.v1, w.hist, M, bits, true, 0, s);
+    const int rc = w.sort.sort(M, bits, s);
     if (rc != GS_OK) return rc;
-    const uint32_t* ks = (radix_passes(bits) & 1) ? w.k1 : w.k0;
+    const uint32_t* ks = w.sort.sorted_keys(bits);
     const int nb_off = (int)((M + 1 + AIAP_THREADS - 1) / AIAP_THREADS);
     hipLaunchKernelGGL(aiap_offsets_kernel, dim3(nb_off + n_sets + 1), dim3(AIAP_THREADS), 0, s, N, M, ks, w.start, nb_off, nb,
                        n_sets, w.partial, w.badp, w.misc, s0.loss, s1.loss);
@@ -367,10 +330,9 @@ __global__ __launch_bounds__(AIAP_THREADS) void aiap_bwd_kernel(int N, int K, co
 
 static int launch_aiap_backward(int N, int K, const long long* idx, int n_sets, const GsAiapSet* sets, const void* workspace,
                                 hipStream_t s) {
-    AiapWs w;
-    aiap_carve(N, K, (char*)const_cast<void*>(workspace), &w);
+    const AiapWs w = aiap_carve(N, K, const_cast<void*>(workspace));
     const long long M = (long long)N * (K - 1);
-    const uint32_t* src = (radix_passes(aiap_bits(N)) & 1) ? w.v1 : w.v0;
+    const uint32_t* src = w.sort.sorted_vals(aiap_bits(N));
     const float inv_m = (float)(1.0 / (double)M);
     const AiapSet s0 = aiap_set(&sets[0]), s1 = aiap_set(n_sets > 1 ? &sets[1] : nullptr);
     const int nb = aiap_blocks(N);

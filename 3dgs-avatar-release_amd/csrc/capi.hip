@@ -3,6 +3,7 @@
 // capture query.  Host-side sequencing of the stages; no device allocation, no implicit synchronisation (except in debug mode).
 #include "common.h"
 #include "boundary.h"
+#include "sorted_lists.h"
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
@@ -331,7 +332,7 @@ static int forward_phase1(const GsFwdArgs* a, void* geom, size_t geom_bytes, voi
             rc = launch_sort_pairs(g.key0, g.val0, g.key1, g.val1, g.hist, a->P, 32, true, a->debug, s); }
             if (rc != GS_OK) return rc;
             { StageScope sc_("rank_list", s);
-            rc = launch_rank_list(g.val0, g.rec, g.tiles, g.ranklist, g.chunk_pairs, a->P, a->debug, s); }
+            rc = launch_rank_list(PairSort{g.key0, g.val0, g.key1, g.val1, g.hist}.sorted_vals(32), g.rec, g.tiles, g.ranklist, g.chunk_pairs, a->P, a->debug, s); }
             if (rc != GS_OK) return rc;
         }
     }

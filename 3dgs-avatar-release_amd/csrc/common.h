@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <type_traits>
 #include "../../include/gsplat_mi355.h"
+#include "ordered_sum.h"  // the wave primitives, ZeroJob, the fixed-order sums
 
 #define TILE 16                 // tile edge in pixels (parity contract: 16x16)
 #define WAVE 64                 // CDNA wavefront
@@ -16,6 +17,19 @@
 // same carve, so the library keeps no pointers between calls (re-entrant, graph-capturable).
 // ---------------------------------------------------------------------------------------------
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Workspace carving of the auxiliary modules: fields in the order they are taken, each starting 256-byte aligned; `o` is
+// the running offset and, at the end, the workspace's size.  A null base sizes only (take returns null).
+struct Carver {
+    char* base;
+    size_t o = 0;
+    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+    template <class T>
+    T* take(size_t count) {
+        const size_t at = o;
+        o = align_up(o + count * sizeof(T), 256);
+        return base ? reinterpret_cast<T*>(base + at) : nullptr;
+    }
+};
 
 #define SORT_ITEMS 4096          // elements per radix-sort block (256 threads x 16)
 #define SORT_SMALL_N (1 << 20)   // sorts up to this size use 1024-element blocks instead
@@ -363,71 +377,6 @@ int gs_zero_async(void* ptr, size_t bytes, const char* stage, hipStream_t s);
 // Per-stage hipEvent timing (gs_profile_enable / gs_profile_collect); a no-op unless enabled.
 void gs_prof_begin(const char* stage, hipStream_t s);
 void gs_prof_end(hipStream_t s);
-// a word range some kernel clears on the side (grid-stride), saving a fill launch
-struct ZeroJob { uint32_t* ptr; int words; };
-// Inclusive prefix sum over the 64 lanes of a wave by DPP row shifts and row broadcasts (six dependent VALU instructions;
-// a __shfl_up ladder is six ds_bpermute round trips through the LDS unit, ~10 x the latency -- and the short binning
-// kernels are nothing but latency).  Every lane must be active.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-    x += dpp_or_zero<0x111, 0xF>(x);  // row_shr:1
-    x += dpp_or_zero<0x112, 0xF>(x);  // row_shr:2
-    x += dpp_or_zero<0x114, 0xF>(x);  // row_shr:4
-    x += dpp_or_zero<0x118, 0xF>(x);  // row_shr:8
-    x += dpp_or_zero<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
-    x += dpp_or_zero<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
-    return x;
-}
-// the same inside every row of 16 lanes
-__device__ __forceinline__ uint32_t row_scan_incl(uint32_t x) {
-    x += dpp_or_zero<0x111, 0xF>(x);
-    x += dpp_or_zero<0x112, 0xF>(x);
-    x += dpp_or_zero<0x114, 0xF>(x);
-    x += dpp_or_zero<0x118, 0xF>(x);
-    return x;
-}
-__device__ __forceinline__ unsigned long long wave_scan_incl(unsigned long long x) {
-    // (two 32-bit ladders would lose the carries: shift the halves, add as 64-bit)
-#define GS_SCAN64_STEP(CTRL, MASK)                                                                           \
-    x += (unsigned long long)dpp_or_zero<CTRL, MASK>((uint32_t)x) |                                          \
-         ((unsigned long long)dpp_or_zero<CTRL, MASK>((uint32_t)(x >> 32)) << 32);
-    GS_SCAN64_STEP(0x111, 0xF) GS_SCAN64_STEP(0x112, 0xF) GS_SCAN64_STEP(0x114, 0xF) GS_SCAN64_STEP(0x118, 0xF)
-    GS_SCAN64_STEP(0x142, 0xA) GS_SCAN64_STEP(0x143, 0xC)
-#undef GS_SCAN64_STEP
-    return x;
-}
-
-// Wave-wide sum / max / min by the same ladder (the result is wave-uniform: lane 63 of the inclusive scan).
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(x), 63); }
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-    x = wave_scan_incl(x);
-    return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63) |
-           ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), 63) << 32);
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t x) {
-    x = max(x, dpp_or_zero<0x111, 0xF>(x));
-    x = max(x, dpp_or_zero<0x112, 0xF>(x));
-    x = max(x, dpp_or_zero<0x114, 0xF>(x));
-    x = max(x, dpp_or_zero<0x118, 0xF>(x));
-    x = max(x, dpp_or_zero<0x142, 0xA>(x));
-    x = max(x, dpp_or_zero<0x143, 0xC>(x));
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t x) { return ~wave_max(~x); }
-// (float: the sum is taken in the ladder's fixed order -- the same bits on every run; lane 63 of the scan holds it)
-__device__ __forceinline__ float wave_scan_incl(float x) {
-#define GS_FSUM_STEP(CTRL, MASK) x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, MASK, 0xF, false));
-    GS_FSUM_STEP(0x111, 0xF) GS_FSUM_STEP(0x112, 0xF) GS_FSUM_STEP(0x114, 0xF) GS_FSUM_STEP(0x118, 0xF)
-    GS_FSUM_STEP(0x142, 0xA) GS_FSUM_STEP(0x143, 0xC)
-#undef GS_FSUM_STEP
-    return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_scan_incl(x)), 63));
-}
 
 // ---- rank segments (binning.hip).  The ranking is cut into `nseg` SEGMENTS of about equal work, not of equal length: the
 // nearest Gaussians come first and cover hundreds of tiles each, so equal-length segments leave the workgroups of the
@@ -503,9 +452,6 @@ __device__ __forceinline__ uint32_t xcc_id() {
     uint32_t v;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(v));
     return v & 7u;
-}
-__device__ __forceinline__ void zero_job(const ZeroJob z) {
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < z.words; k += gridDim.x * blockDim.x) z.ptr[k] = 0u;
 }
 
 // The frame's pair count (num_rendered) as the binning kernels see it: read from the geom state on the DEVICE, so that

@@ -51,7 +51,6 @@
 #define DNF_CLONE_KEPT ((uint32_t)GS_DENSIFY_F_CLONE_KEPT)
 #define DNF_CHILDREN_KEPT ((uint32_t)GS_DENSIFY_F_CHILDREN_KEPT)
 
-static inline size_t dn_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int dn_blocks(int N) { return (N + DN_BLOCK - 1) / DN_BLOCK; }
 
 // workspace layout: flags u8[N] | block counts u32[3, blocks] | block offsets u32[3, blocks] | totals u32[4] |
@@ -63,20 +62,17 @@ struct DnWs {
     uint32_t* totals;  // n_keep, n_clone, n_child, N'
     uint32_t* map;
 };
-static inline size_t dn_carve(int N, char* base, DnWs* w) {
+static inline size_t dn_carve(int N, void* base, DnWs* w) {
     const size_t nb = (size_t)dn_blocks(N);
-    size_t o = 0;
-    if (w) w->flags = (uint8_t*)(base + o);
-    o += dn_align((size_t)N);
-    if (w) w->counts = (uint32_t*)(base + o);
-    o += dn_align(3 * nb * 4);
-    if (w) w->offsets = (uint32_t*)(base + o);
-    o += dn_align(3 * nb * 4);
-    if (w) w->totals = (uint32_t*)(base + o);
-    o += dn_align(4 * 4);
-    if (w) w->map = (uint32_t*)(base + o);
-    o += dn_align(2 * (size_t)N * 4);
-    return o;
+    Carver c(base);
+    DnWs ws;
+    ws.flags = c.take<uint8_t>((size_t)N);
+    ws.counts = c.take<uint32_t>(3 * nb);
+    ws.offsets = c.take<uint32_t>(3 * nb);
+    ws.totals = c.take<uint32_t>(4);
+    ws.map = c.take<uint32_t>(2 * (size_t)N);
+    if (w) *w = ws;
+    return c.o;
 }
 static size_t densify_workspace_bytes(int N) { return dn_carve(N, nullptr, nullptr); }
 

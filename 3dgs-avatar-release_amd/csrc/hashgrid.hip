@@ -41,7 +41,7 @@
 //                   every level, written once), and the (key = offset_l + entry_k, value = 8 i + k) pair of every corner at
 //                   position (l N + i) 8 + k.  It also clears the sort's digit totals (no memset node).
 //   radix sort      radix_sort.hip, stable LSD on the key bits: the pairs of one entry stay in (l, i, k) order.
-//   hg_starts       start[e], e = 0 .. n_entries, the first sorted pair whose key is >= e (gap filling, as aiap.hip).
+//   hg_starts       start[e], e = 0 .. n_entries, the first sorted pair whose key is >= e (list_starts: sorted_lists.h).
 //   hg_chunks       a wave per chunk of HG_CHUNK sorted pairs: for the (at most two) lists longer than HG_CHUNK that
 //                   reach into the chunk, the sum of their pairs inside it (lane-strided, then the DPP ladder).
 //   hg_entries      one thread per entry writes its F gradient words once (an empty list writes 0): up to HG_HEAVY
@@ -50,6 +50,8 @@
 // Every order is fixed: the same input gives the same bits, run after run and under graph replay.
 #include "common.h"
 #include "boundary.h"
+#include "ordered_sum.h"
+#include "sorted_lists.h"
 
 #define HG_THREADS 256
 #ifndef HG_HEAVY
@@ -58,8 +60,6 @@
 #ifndef HG_CHUNK
 #define HG_CHUNK 1024  // pairs per chunk: lists longer than this are summed from chunk partials
 #endif
-
-static inline size_t hg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- the level table (host), passed to the kernels by value; hashgrid_table is the one source of the integer decisions
 struct HgTable {
@@ -103,32 +103,25 @@ static inline int hg_bits(uint32_t n) {  // bits of a key in [0, n)
     return b;
 }
 
-// workspace: keys / values u32[2][2][M] (the sort's ping-pong buffers), M = 8 L N | sort tables | start u32[n_entries + 1]
+// workspace: the pair sort's buffers and tables for M = 8 L N pairs (PairSort) | start u32[n_entries + 1]
 // | chunk partials f32[chunks][2][F]
 struct HgWs {
-    uint32_t *k0, *v0, *k1, *v1;
-    uint32_t* hist;
+    PairSort sort;
     uint32_t* start;
     float* part;
+    size_t total;
 };
-static inline size_t hg_carve(const HgTable& t, int N, char* base, HgWs* w) {
+static inline HgWs hg_carve(const HgTable& t, int N, void* base) {
     const size_t M = (size_t)8 * t.L * (size_t)N, nch = (M + HG_CHUNK - 1) / HG_CHUNK;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += hg_align(bytes); return p; };
-    char* k0 = take(M * 4);
-    char* v0 = take(M * 4);
-    char* k1 = take(M * 4);
-    char* v1 = take(M * 4);
-    char* hist = take(sort_table_words(M) * 4);
-    char* start = take(((size_t)t.off[t.L] + 1) * 4);
-    char* part = take(nch * 2 * t.F * 4);
-    if (w) {
-        w->k0 = (uint32_t*)k0; w->v0 = (uint32_t*)v0; w->k1 = (uint32_t*)k1; w->v1 = (uint32_t*)v1;
-        w->hist = (uint32_t*)hist; w->start = (uint32_t*)start; w->part = (float*)part;
-    }
-    return o;
+    Carver c(base);
+    HgWs w;
+    w.sort = PairSort::carve(c, M);
+    w.start = c.take<uint32_t>((size_t)t.off[t.L] + 1);
+    w.part = c.take<float>(nch * 2 * t.F);
+    w.total = c.o;
+    return w;
 }
-static size_t hashgrid_workspace_bytes(const HgTable& t, int N) { return hg_carve(t, N, nullptr, nullptr); }
+static size_t hashgrid_workspace_bytes(const HgTable& t, int N) { return hg_carve(t, N, nullptr).total; }
 
 // ---- device helpers
 template <int F>
@@ -305,31 +298,10 @@ __global__ __launch_bounds__(HG_THREADS) void hg_points_kernel(HgTable tab, int 
     }
 }
 
-// start[e], e = 0 .. n_entries, from the sorted keys (every word written once: by the pair that ends the gap in front of
-// it; gaps longer than a wave are filled by the whole wave)
+// start[e], e = 0 .. n_entries, from the sorted keys: list_starts (sorted_lists.h), one thread per pair
 __global__ __launch_bounds__(HG_THREADS) void hg_starts_kernel(uint32_t n_entries, long long M, const uint32_t* __restrict__ ks,
                                                                uint32_t* __restrict__ start) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    const long long q = (long long)blockIdx.x * HG_THREADS + threadIdx.x;  // q = M: a virtual pair of key n_entries
-    const bool valid = q <= M;
-    long long lo = 0, hi = -1;  // this pair writes start[lo .. hi] = q
-    if (valid) {
-        const long long key = q < M ? (long long)ks[q] : (long long)n_entries;
-        const long long prev = q > 0 ? (long long)ks[q - 1] : -1;
-        lo = prev + 1;
-        hi = key;
-    }
-    const bool big = hi - lo + 1 > WAVE;
-    if (!big)
-        for (long long t = lo; t <= hi; t++) start[t] = (uint32_t)q;
-    unsigned long long bal = __ballot(big);
-    while (bal) {  // (wave-uniform)
-        const int L = __ffsll((long long)bal) - 1;
-        bal &= bal - 1;
-        const long long blo = (long long)__shfl((int)lo, L), bhi = (long long)__shfl((int)hi, L);
-        const uint32_t bq = (uint32_t)__shfl((int)q, L);
-        for (long long t = blo + lane; t <= bhi; t += WAVE) start[t] = bq;
-    }
+    list_starts(ks, M, n_entries, (long long)blockIdx.x * HG_THREADS + threadIdx.x, start);
 }
 
 // lane-strided sum of the contributions of sorted pairs [a, b) to an entry of level l, then the DPP ladder (wave-uniform
@@ -455,29 +427,27 @@ __global__ __launch_bounds__(HG_THREADS) void hg_entries_kernel(HgTable tab, int
 template <int F>
 static int hg_backward(const HgTable& tab, int N, const float* x, const float* params, const float* dL_dout, float* dL_dx,
                        float* dL_dparams, void* workspace, hipStream_t s) {
-    HgWs w;
-    hg_carve(tab, N, (char*)workspace, &w);
+    const HgWs w = hg_carve(tab, N, workspace);
     const long long M = 8ll * tab.L * N;
     const uint32_t n_entries = tab.off[tab.L];
     const int bits = hg_bits(n_entries);
     ZeroJob zj{nullptr, 0};
-    if (dL_dparams) sort_totals_region(w.hist, M, bits, &zj.ptr, &zj.words);
+    if (dL_dparams) zj = w.sort.totals_job(M, bits);
     const int nb = N > 0 ? (N + HG_THREADS - 1) / HG_THREADS : 1;
     {
         StageScope st("hashgrid_points", s);
         hipLaunchKernelGGL(hg_points_kernel<F>, dim3(nb), dim3(HG_THREADS), 0, s, tab, N, x, params, dL_dout, dL_dx,
-                           dL_dparams ? w.k0 : nullptr, w.v0, zj);
+                           dL_dparams ? w.sort.k0 : nullptr, w.sort.v0, zj);
         GS_LAUNCH_CHECK("hashgrid_points", 0, s);
     }
     if (!dL_dparams) return GS_OK;
     {
         StageScope st("hashgrid_sort", s);
-        const int rc = launch_sort_pairs(w.k0, w.v0, w.k1, w.v1, w.hist, M, bits, true, 0, s);
+        const int rc = w.sort.sort(M, bits, s);
         if (rc != GS_OK) return rc;
     }
-    const bool odd = radix_passes(bits) & 1;
-    const uint32_t* ks = odd && M > 0 ? w.k1 : w.k0;
-    const uint32_t* src = odd && M > 0 ? w.v1 : w.v0;
+    const uint32_t* ks = w.sort.sorted_keys(bits);
+    const uint32_t* src = w.sort.sorted_vals(bits);
     StageScope st("hashgrid_sum", s);
     const int nb_st = (int)((M + 1 + HG_THREADS - 1) / HG_THREADS);
     hipLaunchKernelGGL(hg_starts_kernel, dim3(nb_st), dim3(HG_THREADS), 0, s, n_entries, M, ks, w.start);

@@ -10,35 +10,40 @@
 // point inside the box.  Built with -ffp-contract=off so distances match the CPU oracle bit for bit.
 #include "common.h"
 #include "boundary.h"
+#include "sorted_lists.h"
 #include <float.h>
 
 #define KNN_BOX 64   // points per box of the Morton-ordered reference set (one point per lane of the search's wave)
 #define KNN_WAVE 64  // the search kernels run one wave per workgroup: their barriers and votes are wave-level
 #define KNN_MM_BLOCKS 128  // blocks of the bounding-box pass; each leaves its own partial (no atomics, nothing to clear)
 
-struct KnnLayout {
-    size_t key0, key1, val0, val1, hist, pts, boxes, minmax, total;
-    int nblk_sort, nbox;
+// workspace: the Morton sort's buffers (both key buffers in front of the value buffers, as this layout always had them:
+// its own order of takes, not PairSort::carve's) and tables | sorted points | boxes | partial bounding boxes
+struct KnnWs {
+    PairSort sort;
+    float4* pts;
+    float* boxes;
+    float* minmax;
+    size_t total;
+    int nbox;
 };
-static KnnLayout knn_layout(int P) {
-    KnnLayout L;
-    size_t o = 0;
-    size_t n = (size_t)(P > 0 ? P : 1);
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    L.nblk_sort = (int)((n + SORT_ITEMS - 1) / SORT_ITEMS);
-    L.nbox = (int)((n + KNN_BOX - 1) / KNN_BOX);
-    L.key0 = take(n * 4);
-    L.key1 = take(n * 4);
-    L.val0 = take(n * 4);
-    L.val1 = take(n * 4);
-    L.hist = take(sort_table_words(n) * 4);
-    L.pts = take(n * 16);
-    L.boxes = take((size_t)L.nbox * 32);
-    L.minmax = take((size_t)KNN_MM_BLOCKS * 6 * 4);
-    L.total = o;
-    return L;
+static KnnWs knn_carve(int P, void* base) {
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    Carver c(base);
+    KnnWs w;
+    w.nbox = (int)((n + KNN_BOX - 1) / KNN_BOX);
+    w.sort.k0 = c.take<uint32_t>(n);
+    w.sort.k1 = c.take<uint32_t>(n);
+    w.sort.v0 = c.take<uint32_t>(n);
+    w.sort.v1 = c.take<uint32_t>(n);
+    w.sort.hist = c.take<uint32_t>(sort_table_words(n));
+    w.pts = c.take<float4>(n);
+    w.boxes = c.take<float>((size_t)w.nbox * 8);
+    w.minmax = c.take<float>((size_t)KNN_MM_BLOCKS * 6);
+    w.total = c.o;
+    return w;
 }
-static size_t knn_ws_bytes(int P) { return knn_layout(P).total; }
+static size_t knn_ws_bytes(int P) { return knn_carve(P, nullptr).total; }
 
 // partial bounding boxes: mm[6 b .. 6 b + 5] = (min xyz, max xyz) of block b's grid-stride share
 // (also clears the radix sort's digit totals on the side: a fill launch less)
@@ -401,37 +406,31 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_scan_kernel(int Nq, const float*
     }
 }
 
+// the reference set in Morton order with its boxes: bounding box, Morton keys, their sort, gather (what both searches start with)
+static int knn_sorted_boxes(const KnnWs& L, int P, const float* points, hipStream_t s) {
+    const int nb = (P + 255) / 256;
+    const int nparts = nb < KNN_MM_BLOCKS ? nb : KNN_MM_BLOCKS;
+    hipLaunchKernelGGL(knn_minmax_kernel, dim3(nparts), dim3(256), 0, s, P, points, L.minmax, L.sort.totals_job(P, KNN_MORTON_BITS));
+    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, s, P, points, L.minmax, nparts, L.sort.k0, L.sort.v0);
+    GS_LAUNCH_CHECK("knn.morton", 0, s);
+    const int rc = L.sort.sort(P, KNN_MORTON_BITS, s);
+    if (rc != GS_OK) return rc;
+    hipLaunchKernelGGL(knn_gather_box_kernel, dim3(nb), dim3(256), 0, s, P, points, L.sort.sorted_vals(KNN_MORTON_BITS), L.pts, L.boxes);
+    return GS_OK;
+}
+
 static int launch_knn_points(int Nq, const float* queries, int Nr, const float* ref, int K, float* out_d, long long* out_i,
                              void* ws, size_t ws_bytes, hipStream_t s) {
-    const KnnLayout L = knn_layout(Nr);
+    const KnnWs L = knn_carve(Nr, ws);
     if (ws_bytes < L.total) return GS_E_WORKSPACE;
-    char* w = (char*)ws;
-    uint32_t* k0 = (uint32_t*)(w + L.key0);
-    uint32_t* k1 = (uint32_t*)(w + L.key1);
-    uint32_t* v0 = (uint32_t*)(w + L.val0);
-    uint32_t* v1 = (uint32_t*)(w + L.val1);
-    uint32_t* hist = (uint32_t*)(w + L.hist);
-    float4* sp = (float4*)(w + L.pts);
-    float* boxes = (float*)(w + L.boxes);
-    float* mm = (float*)(w + L.minmax);
-    const int nb = (Nr + 255) / 256;
     StageScope st("knn_points", s);
-    const int nparts = nb < KNN_MM_BLOCKS ? nb : KNN_MM_BLOCKS;
-    ZeroJob zt;
-    sort_totals_region(hist, Nr, KNN_MORTON_BITS, &zt.ptr, &zt.words);
-    hipLaunchKernelGGL(knn_minmax_kernel, dim3(nparts), dim3(256), 0, s, Nr, ref, mm, zt);
-    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, s, Nr, ref, mm, nparts, k0, v0);
-    GS_LAUNCH_CHECK("knn.morton", 0, s);
-    int rc = launch_sort_pairs(k0, v0, k1, v1, hist, Nr, KNN_MORTON_BITS, true, 0, s);
-    if (rc != GS_OK) return rc;
-    const uint32_t* order = (radix_passes(KNN_MORTON_BITS) & 1) ? v1 : v0;
-    hipLaunchKernelGGL(knn_gather_box_kernel, dim3(nb), dim3(256), 0, s, Nr, ref, order, sp, boxes);
+    if (const int rc = knn_sorted_boxes(L, Nr, ref, s)) return rc;
     const int self = (queries == ref && Nq == Nr) ? 1 : 0;
     // queries per wave: enough waves to give every SIMD a few (1024 SIMDs)
     const int qpw = Nq >= (1 << 18) ? 64 : (Nq >= (1 << 17) ? 32 : 16);
 #define KNN_LAUNCH_Q(KK, QQ)                                                                                             \
     hipLaunchKernelGGL((knn_scan_kernel<KK, false, QQ>), dim3((Nq + QQ - 1) / QQ), dim3(KNN_WAVE), 0, s, Nq, queries, self, \
-                       Nr, L.nbox, sp, boxes, out_d, out_i)
+                       Nr, L.nbox, L.pts, L.boxes, out_d, out_i)
 #define KNN_LAUNCH(KK)                                                                                                   \
     case KK:                                                                                                             \
         if (qpw == 64) KNN_LAUNCH_Q(KK, 64);                                                                             \
@@ -449,37 +448,18 @@ static int launch_knn_points(int Nq, const float* queries, int Nr, const float* 
 }
 
 static int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    const KnnLayout L = knn_layout(P);
+    const KnnWs L = knn_carve(P, ws);
     if (ws_bytes < L.total) return GS_E_WORKSPACE;
-    char* w = (char*)ws;
-    uint32_t* k0 = (uint32_t*)(w + L.key0);
-    uint32_t* k1 = (uint32_t*)(w + L.key1);
-    uint32_t* v0 = (uint32_t*)(w + L.val0);
-    uint32_t* v1 = (uint32_t*)(w + L.val1);
-    uint32_t* hist = (uint32_t*)(w + L.hist);
-    float4* sp = (float4*)(w + L.pts);
-    float* boxes = (float*)(w + L.boxes);
-    float* mm = (float*)(w + L.minmax);
-    const int nb = (P + 255) / 256;
-    const int nparts = nb < KNN_MM_BLOCKS ? nb : KNN_MM_BLOCKS;
-    ZeroJob zt;
-    sort_totals_region(hist, P, KNN_MORTON_BITS, &zt.ptr, &zt.words);
-    hipLaunchKernelGGL(knn_minmax_kernel, dim3(nparts), dim3(256), 0, s, P, points, mm, zt);
-    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, s, P, points, mm, nparts, k0, v0);
-    GS_LAUNCH_CHECK("knn.morton", 0, s);
-    int rc = launch_sort_pairs(k0, v0, k1, v1, hist, P, KNN_MORTON_BITS, true, 0, s);
-    if (rc != GS_OK) return rc;
-    const uint32_t* order = (radix_passes(KNN_MORTON_BITS) & 1) ? v1 : v0;
-    hipLaunchKernelGGL(knn_gather_box_kernel, dim3(nb), dim3(256), 0, s, P, points, order, sp, boxes);
+    if (const int rc = knn_sorted_boxes(L, P, points, s)) return rc;
     if (P >= (1 << 18))
         hipLaunchKernelGGL((knn_scan_kernel<3, true, 64>), dim3((P + 63) / 64), dim3(KNN_WAVE), 0, s, P, (const float*)nullptr, 1,
-                           P, L.nbox, sp, boxes, out, (long long*)nullptr);
+                           P, L.nbox, L.pts, L.boxes, out, (long long*)nullptr);
     else if (P >= (1 << 17))
         hipLaunchKernelGGL((knn_scan_kernel<3, true, 32>), dim3((P + 31) / 32), dim3(KNN_WAVE), 0, s, P, (const float*)nullptr, 1,
-                           P, L.nbox, sp, boxes, out, (long long*)nullptr);
+                           P, L.nbox, L.pts, L.boxes, out, (long long*)nullptr);
     else
         hipLaunchKernelGGL((knn_scan_kernel<3, true, 16>), dim3((P + 15) / 16), dim3(KNN_WAVE), 0, s, P, (const float*)nullptr, 1,
-                           P, L.nbox, sp, boxes, out, (long long*)nullptr);
+                           P, L.nbox, L.pts, L.boxes, out, (long long*)nullptr);
     GS_LAUNCH_CHECK("knn.search", 0, s);
     return GS_OK;
 }

@@ -1,9 +1,10 @@
 // loss.hip -- image-side L1 loss (replaces utils/loss_utils.py:21-22,
 // torch.abs(network_output - gt).mean(), and its autograd chain of ~10 elementwise kernels).
 // One streaming pass writes d(loss)/d(network_output) = sign(x - y) / n and one partial sum of
-// |x - y| per block; a second, single-block pass adds the partials in index order.  No atomics: the
-// result is bitwise reproducible.
+// |x - y| per block; a second, single-block pass adds the partials -- the schemes of block_sum (waves
+// pairwise) and ordered_final_kernel in ordered_sum.h.  No atomics: the result is bitwise reproducible.
 #include "common.h"
+#include "ordered_sum.h"
 #include "boundary.h"
 #include <math.h>
 
@@ -35,12 +36,15 @@ __global__ __launch_bounds__(L1_THREADS) void l1_partial_kernel(const float* __r
         acc += fabsf(d);
         grad[i] = sgn_over_n(d, inv_n);
     }
-    acc = wave_sum(acc);
+    acc = wave_sum(acc);  // (block_sum<L1_THREADS, WavesPairwise> in this kernel's own text: see l1_final_kernel)
     if (lane == 0) ws[wid] = acc;
     __syncthreads();
     if (tid == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 
+// The second pass of the L1 / BCE / SSIM means, one workgroup: what ordered_final_kernel<L1_THREADS, WavesPairwise, true>
+// computes for q = 0.  It and l1_partial_kernel run in every training step and keep their own text: written with
+// block_sum they compile to one instruction less, and the step's kernels are held to the instructions they were measured with.
 __global__ __launch_bounds__(L1_THREADS) void l1_final_kernel(const float* __restrict__ partial, int nparts, float inv_n,
                                                               float* __restrict__ loss) {
     __shared__ float ws[L1_THREADS / 64];
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(L1_THREADS) void l1_final_kernel(const float* __res
     acc = wave_sum(acc);
     if (lane == 0) ws[wid] = acc;
     __syncthreads();
-    if (tid == 0) loss[0] = ((ws[0] + ws[1]) + (ws[2] + ws[3])) * inv_n;
+    if (tid == 0) loss[0] = ((ws[0] + ws[1]) + (ws[2] + ws[3])) * inv_n;  // (WavesPairwise)
 }
 
 // Mask loss, BCE form (train.py:146-148): F.binary_cross_entropy(torch.clamp(x, 1e-3, 1 - 1e-3), y), mean over all
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(L1_THREADS) void bce_partial_kernel(const float* __
                                                                  int64_t n, float inv_n, float* __restrict__ grad,
                                                                  float* __restrict__ partial) {
     __shared__ float ws[L1_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     float acc = 0.f;
     const int64_t stride = (int64_t)gridDim.x * L1_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * L1_THREADS + tid; i < n; i += stride) {
@@ -70,10 +74,8 @@ __global__ __launch_bounds__(L1_THREADS) void bce_partial_kernel(const float* __
         const bool inside = xv >= 1.0e-3f && xv <= 1.0f - 1.0e-3f;  // clamp passes the gradient on its closed range
         grad[i] = inside ? (p - t) / (p * (1.0f - p)) * inv_n : 0.f;
     }
-    acc = wave_sum(acc);
-    if (lane == 0) ws[wid] = acc;
-    __syncthreads();
-    if (tid == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    const float s = block_sum<L1_THREADS, WavesPairwise>(acc, ws);
+    if (tid == 0) partial[blockIdx.x] = s;
 }
 
 static int l1_blocks(int64_t n) {
@@ -97,7 +99,9 @@ static int launch_bce_loss(const float* x, const float* y, int64_t n, float* los
 // The same sum for MANY partials (the fused L1: one per quadrant, 16 384 at 1024 x 1024): one workgroup of 1024 threads, every
 // thread's loads requested eight at a time before they are added (as a plain strided loop over 256 threads the launch took
 // 16 us at config 3: 64 dependent round trips per thread).  Fixed order: thread t adds its partials t, t + 1024, ... in
-// index order, the threads' sums go through the DPP ladder and the 16 wave sums are added in wave order.
+// index order, the threads' sums go through the DPP ladder and the 16 wave sums are added in wave order STARTING FROM 0
+// (0 + w0 + w1 ...: one addition more than block_sum<1024, WavesInOrder>, under which sixteen -0 would stay -0; the
+// kernel runs in every training step and keeps its text).
 __global__ __launch_bounds__(1024) void loss_final_wide_kernel(const float* __restrict__ partial, int nparts, float inv_n,
                                                                float* __restrict__ loss) {
     __shared__ float ws[16];
@@ -271,22 +275,8 @@ __global__ __launch_bounds__(SS_NT) void ssim_fwd_kernel(int H, int W, const flo
             }
         }
     }
-    val = wave_sum(val);
-    if ((tid & 63) == 0) ws[tid >> 6] = val;
-    __syncthreads();
-    if (tid == 0) partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
-
-__global__ __launch_bounds__(256) void ssim_final_kernel(const float* __restrict__ partial, int nparts, float inv_n,
-                                                         float* __restrict__ out) {
-    __shared__ float ws[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    float acc = 0.f;
-    for (int i = tid; i < nparts; i += 256) acc += partial[i];
-    acc = wave_sum(acc);
-    if (lane == 0) ws[wid] = acc;
-    __syncthreads();
-    if (tid == 0) out[0] = ((ws[0] + ws[1]) + (ws[2] + ws[3])) * inv_n;
+    val = block_sum<SS_NT, WavesPairwise>(val, ws);
+    if (tid == 0) partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = val;
 }
 
 // dL/dimg1(p) = g/n * sum_q w(q - p) [ dm_dmu1(q) + 2 img1(p) dm_ds1(q) + img2(p) dm_ds12(q) ]
@@ -403,7 +393,7 @@ static int launch_ssim_forward(int C, int H, int W, const float* img1, const flo
     hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(SS_NT), 0, s, H, W, img1, img2, ssim_window(), dm_dmu1, dm_ds1,
                        dm_ds12, partial);
     GS_LAUNCH_CHECK("ssim.forward", 0, s);
-    hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.y * grid.z),
+    hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(L1_THREADS), 0, s, partial, (int)(grid.x * grid.y * grid.z),
                        1.0f / ((float)C * (float)H * (float)W), ssim_out);
     GS_LAUNCH_CHECK("ssim.final", 0, s);
     return GS_OK;

@@ -49,10 +49,9 @@
 //   bytes, generally do not), moved between global memory and LDS with 16-byte accesses; so is its slab of feature.
 //   nr_apply_fwd   slab -> LDS; one thread per row reads the ten head columns from LDS and writes xyz', scaling',
 //                  rotation'; all threads gather the feature columns from LDS into 16-byte stores; the three norms are
-//                  summed over the block in a fixed order (the DPP ladder per wave, the waves in order) into
-//                  partial[3][blocks].
-//   nr_final       three workgroups, one per regulariser: the block partials in a fixed order, times 1 / N (the scheme
-//                  of loss.hip's loss_final_wide_kernel, for three sums in one launch).
+//                  summed over the block (block_sum, waves in order: ordered_sum.h) into partial[3][blocks].
+//   (final)        three workgroups, one per regulariser, add the block partials: ordered_final_kernel (ordered_sum.h),
+//                  waves in order, times 1 / N.
 //   nr_apply_bwd   builds the block's slab of dL/ddeltas in LDS (head columns by the row's thread, feature columns
 //                  scattered from 16-byte loads of the upstream feature slab) and stores it with 16-byte accesses.  The
 //                  ten head columns of deltas are read from global memory directly (40 bytes a row).
@@ -60,6 +59,8 @@
 // capture-safe.
 #include "common.h"
 #include "boundary.h"
+#include "ordered_sum.h"
+#include "slab.h"
 
 // ---------------------------------------------------------------------------------------------
 // 1. the pose encoder
@@ -332,13 +333,7 @@ __global__ __launch_bounds__(NR_THREADS) void nr_apply_fwd_kernel(int N, int D, 
     const int t = threadIdx.x, F = D - 10;
     const size_t row0 = (size_t)blockIdx.x * R;
     const int n = (int)min((size_t)R, (size_t)N - row0);
-    {
-        const size_t off = row0 * D;
-        const int total = n * D, n4 = total >> 2;
-        const float4* g4 = reinterpret_cast<const float4*>(deltas + off);
-        for (int k = t; k < n4; k += NR_THREADS) buf4[k] = g4[k];
-        for (int k = 4 * n4 + t; k < total; k += NR_THREADS) buf[k] = deltas[off + k];
-    }
+    slab_load<NR_THREADS>(deltas + row0 * D, n * D, buf);
     __syncthreads();
     float lx = 0.0f, ls = 0.0f, lr = 0.0f;
     if (t < n) {
@@ -392,39 +387,11 @@ __global__ __launch_bounds__(NR_THREADS) void nr_apply_fwd_kernel(int N, int D, 
         }
         for (int f = 4 * n4 + t; f < total; f += NR_THREADS) feat[foff + f] = buf[(f / F) * D + 10 + f % F];
     }
-    if (partial) {  // (uniform; every lane takes part in the ladders: the rows past n add zeros)
-        lx = wave_sum(lx);
-        ls = wave_sum(ls);
-        lr = wave_sum(lr);
-        if ((t & 63) == 0) {
-            s_red[0][t >> 6] = lx;
-            s_red[1][t >> 6] = ls;
-            s_red[2][t >> 6] = lr;
-        }
-        __syncthreads();
-        if (t < 3) {
-            float acc = s_red[t][0];
-            for (int w = 1; w < NR_THREADS / 64; w++) acc += s_red[t][w];
-            partial[(size_t)t * gridDim.x + blockIdx.x] = acc;
-        }
-    }
-}
-
-// loss[q] = (partial[q][0] + ... + partial[q][nb - 1], in a fixed order) / N, q = blockIdx.x
-__global__ __launch_bounds__(NR_THREADS) void nr_final_kernel(const float* __restrict__ partial, int nb, float inv_n,
-                                                              float* __restrict__ loss) {
-    __shared__ float ws[NR_THREADS / 64];
-    const int t = threadIdx.x;
-    const float* p = partial + (size_t)blockIdx.x * nb;
-    float acc = 0.0f;
-    for (int i = t; i < nb; i += NR_THREADS) acc += p[i];
-    acc = wave_sum(acc);
-    if ((t & 63) == 0) ws[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) {
-        float s = ws[0];
-        for (int w = 1; w < NR_THREADS / 64; w++) s += ws[w];
-        loss[blockIdx.x] = s * inv_n;
+    if (partial) {  // (uniform; every lane takes part in the sums: the rows past n add zeros)
+        const float sums[3] = {block_sum<NR_THREADS, WavesInOrder>(lx, s_red[0]), block_sum<NR_THREADS, WavesInOrder>(ls, s_red[1]),
+                               block_sum<NR_THREADS, WavesInOrder>(lr, s_red[2])};
+        if (t == 0)
+            for (int q = 0; q < 3; q++) partial[(size_t)q * gridDim.x + blockIdx.x] = sums[q];
     }
 }
 
@@ -518,11 +485,7 @@ __global__ __launch_bounds__(NR_THREADS) void nr_apply_bwd_kernel(int N, int D, 
     }
     if (ddeltas) {  // (uniform)
         __syncthreads();
-        const size_t off = row0 * D;
-        const int total = n * D, n4 = total >> 2;
-        float4* g4 = reinterpret_cast<float4*>(ddeltas + off);
-        for (int k = t; k < n4; k += NR_THREADS) g4[k] = buf4[k];
-        for (int k = 4 * n4 + t; k < total; k += NR_THREADS) ddeltas[off + k] = buf[k];
+        slab_store<NR_THREADS>(ddeltas + row0 * D, n * D, buf);
     }
 }
 
@@ -537,7 +500,8 @@ static int launch_nonrigid_apply_forward(int N, int D, int smode, int rmode, con
                        rot, xyz_o, scal_o, rot_o, feat, partial);
     GS_LAUNCH_CHECK("nonrigid_apply", 0, s);
     if (losses) {
-        hipLaunchKernelGGL(nr_final_kernel, dim3(3), dim3(NR_THREADS), 0, s, partial, nb, 1.0f / (float)N, losses);
+        hipLaunchKernelGGL((ordered_final_kernel<NR_THREADS, WavesInOrder, true>), dim3(3), dim3(NR_THREADS), 0, s,
+                           (const float*)partial, nb, 1.0f / (float)N, losses);
         GS_LAUNCH_CHECK("nonrigid_final", 0, s);
     }
     return GS_OK;

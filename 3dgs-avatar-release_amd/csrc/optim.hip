@@ -6,6 +6,7 @@
 //     (lr per group, eps 1e-15): the foreach implementation launches ~10 kernels per group.
 // Here: one streaming kernel for the statistics and ONE launch for the Adam step of all tensors.
 #include "common.h"
+#include "ordered_sum.h"
 #include "boundary.h"
 
 __global__ __launch_bounds__(256) void densify_stats_kernel(int N, const int32_t* __restrict__ radii,
@@ -90,7 +91,8 @@ static int launch_adam(int n, const GsAdamTensor* tensors, double beta1, double 
 // tensors, torch.optim.Adam with weight decay on two groups, and a step number that lives on the device so that the
 // whole step can be captured into a hipGraph.  Four kernels:
 //   grad_sumsq_kernel   one workgroup per fixed 2048-element chunk of one tensor: its sum of squares -> one partial
-//   grad_norm_final     ONE workgroup adds the partials in a fixed order (no atomics) -> total_norm, clip_coef
+//   grad_norm_final     ONE workgroup adds the partials in a fixed order (strided_sum, then block_sum with the waves
+//                       in order: ordered_sum.h; no atomics) -> total_norm, clip_coef
 //   adam_begin_step     one thread per tensor: its device `step` scalar += 1 (a launch of its own in front of the
 //                       update, so that no workgroup of the update races with the increment; an empty tensor's step
 //                       advances too, as torch's does)
@@ -128,14 +130,6 @@ __device__ __forceinline__ int chunk_owner(const int* start, int count, int chun
     return lo;
 }
 
-// workgroup sum of 256 threads in a fixed order: DPP ladder per wave, then the four wave sums in wave order
-__device__ __forceinline__ float block_sum_256(float x, float* lds4) {
-    x = wave_sum(x);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
-
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(GradBatch b, float* __restrict__ partials) {
     __shared__ float lds4[4];
     const int k = chunk_owner(b.start, b.count, (int)blockIdx.x);
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(GradBatch b, float* __r
                 if (i + e < n) acc = __builtin_fmaf(g[i + e], g[i + e], acc);  // (explicit: both paths round alike)
         }
     }
-    const float s = block_sum_256(acc, lds4);
+    const float s = block_sum<256, WavesInOrder>(acc, lds4);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -167,9 +161,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(GradBatch b, float* __r
 __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __restrict__ partials, int n_partials, float max_norm,
                                                               float* __restrict__ out) {
     __shared__ float lds4[4];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
-    const float s = block_sum_256(acc, lds4);
+    const float s = block_sum<256, WavesInOrder>(strided_sum<256>(partials, n_partials), lds4);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(s);
         float coef = max_norm / (norm + 1e-6f);

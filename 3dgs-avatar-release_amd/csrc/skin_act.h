@@ -1,9 +1,10 @@
 // skin_act.h -- what the kernels of skinning.hip and skinloss.hip share: the row widths of the logit kinds, the moves of a
-// block's contiguous slab of rows between global memory and LDS, and the bone-weight activations (the kinematic-tree
+// block's contiguous slab of rows between global memory and LDS (slab.h, by row), and the bone-weight activations (the kinematic-tree
 // softmax and F.softmax) with their reverses.  The spec of the activations is at the top of skinning.hip.  Every
 // translation unit that includes this is built without FMA contraction (build.py STRICT).
 #pragma once
 #include "common.h"
+#include "slab.h"
 
 #define SKIN_THREADS 256
 
@@ -12,24 +13,14 @@ struct SkinKind {
     static constexpr int C = KIND == GS_SKIN_HIERARCHICAL ? 25 : 24;  // row width
 };
 
-// rows [row0, row0 + n) of a (., C) fp32 array <-> LDS, 16-byte accesses (the global slab starts 16-byte aligned)
+// rows [row0, row0 + n) of a (., C) fp32 array <-> LDS (slab.h; row0 is a multiple of SKIN_THREADS: 16-byte aligned)
 template <int C>
-__device__ __forceinline__ void slab_load(const float* __restrict__ g, int row0, int n, float* __restrict__ lds) {
-    const size_t off = (size_t)row0 * C;
-    const int total = n * C, n4 = total >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(g + off);
-    float4* l4 = reinterpret_cast<float4*>(lds);
-    for (int k = threadIdx.x; k < n4; k += SKIN_THREADS) l4[k] = g4[k];
-    for (int k = 4 * n4 + threadIdx.x; k < total; k += SKIN_THREADS) lds[k] = g[off + k];
+__device__ __forceinline__ void skin_slab_load(const float* __restrict__ g, int row0, int n, float* __restrict__ lds) {
+    slab_load<SKIN_THREADS>(g + (size_t)row0 * C, n * C, lds);
 }
 template <int C>
-__device__ __forceinline__ void slab_store(float* __restrict__ g, int row0, int n, const float* __restrict__ lds) {
-    const size_t off = (size_t)row0 * C;
-    const int total = n * C, n4 = total >> 2;
-    float4* g4 = reinterpret_cast<float4*>(g + off);
-    const float4* l4 = reinterpret_cast<const float4*>(lds);
-    for (int k = threadIdx.x; k < n4; k += SKIN_THREADS) g4[k] = l4[k];
-    for (int k = 4 * n4 + threadIdx.x; k < total; k += SKIN_THREADS) g[off + k] = lds[k];
+__device__ __forceinline__ void skin_slab_store(float* __restrict__ g, int row0, int n, const float* __restrict__ lds) {
+    slab_store<SKIN_THREADS>(g + (size_t)row0 * C, n * C, lds);
 }
 template <int C>
 __device__ __forceinline__ void row_from_lds(const float* __restrict__ lds, int t, float* x) {

@@ -32,8 +32,7 @@
 // slab with 16-byte accesses, as in skinning.hip, whose device functions skin_act.h shares):
 //   skin_sample        the sampling above; p_norm and target, and face, bary, p when their pointers are given.
 //   skin_loss_fwd      r_i per row, one double partial per block.
-//   skin_loss_final    one wave: lane l adds its contiguous run of block partials in block order, lane 0 adds the 64 runs
-//                      in lane order and writes loss[0].
+//   skin_loss_final    one wave: runs64_sum (ordered_sum.h) of the block partials, divided by n, into loss[0].
 //   skin_loss_bwd      recomputes W and writes every dlogits row once.
 // No atomics, no memsets, no host reads: every result is bitwise reproducible, and the calls are capture-safe.
 #include "common.h"
@@ -98,8 +97,8 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_sample_kernel(
         for (int c = 0; c < 3; c++) row[3 * t + c] = pn[c];
     }
     __syncthreads();
-    slab_store<24>(target, row0, cnt, tgt);
-    slab_store<3>(p_norm, row0, cnt, row);
+    skin_slab_store<24>(target, row0, cnt, tgt);
+    skin_slab_store<3>(p_norm, row0, cnt, row);
     if (bary_out) {  // (uniform)
         __syncthreads();
         if (t < cnt) {
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_sample_kernel(
             for (int c = 0; c < 3; c++) row[3 * t + c] = bc[c];
         }
         __syncthreads();
-        slab_store<3>(bary_out, row0, cnt, row);
+        skin_slab_store<3>(bary_out, row0, cnt, row);
     }
     if (p_out) {  // (uniform)
         __syncthreads();
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_sample_kernel(
             for (int c = 0; c < 3; c++) row[3 * t + c] = p[c];
         }
         __syncthreads();
-        slab_store<3>(p_out, row0, cnt, row);
+        skin_slab_store<3>(p_out, row0, cnt, row);
     }
 }
 
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_loss_fwd_kernel(int n, cons
     __shared__ double srow[SKIN_THREADS];
     float* buf = reinterpret_cast<float*>(buf4);
     const int row0 = blockIdx.x * SKIN_THREADS, cnt = min(SKIN_THREADS, n - row0), t = threadIdx.x;
-    slab_load<C>(logits, row0, cnt, buf);
+    skin_slab_load<C>(logits, row0, cnt, buf);
     __syncthreads();
     double r = 0.0;
     if (t < cnt) {
@@ -166,17 +165,8 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_loss_fwd_kernel(int n, cons
 __global__ __launch_bounds__(64) void skin_loss_final_kernel(int n, int nb, const double* __restrict__ partial,
                                                              float* __restrict__ loss) {
     __shared__ double run[64];
-    const int l = threadIdx.x;
-    const int per = (nb + 63) / 64, b0 = min(nb, l * per), b1 = min(nb, b0 + per);
-    double a = 0.0;
-    for (int b = b0; b < b1; b++) a += partial[b];
-    run[l] = a;
-    __syncthreads();
-    if (l == 0) {
-        double s = 0.0;
-        for (int k = 0; k < 64; k++) s += run[k];
-        loss[0] = (float)(s / (double)n);
-    }
+    const double s = runs64_sum(partial, nb, run);
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)n);
 }
 
 template <int KIND>
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_loss_bwd_kernel(int n, cons
     __shared__ float4 buf4[SKIN_THREADS * C / 4];
     float* buf = reinterpret_cast<float*>(buf4);
     const int row0 = blockIdx.x * SKIN_THREADS, cnt = min(SKIN_THREADS, n - row0), t = threadIdx.x;
-    slab_load<C>(logits, row0, cnt, buf);
+    skin_slab_load<C>(logits, row0, cnt, buf);
     __syncthreads();
     const float c = (2.0f * dL_dloss[0]) / (float)n;
     float dx[C];
@@ -207,7 +197,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_loss_bwd_kernel(int n, cons
         for (int k = 0; k < C; k++) buf[t * C + k] = dx[k];
     }
     __syncthreads();
-    slab_store<C>(dL_dlogits, row0, cnt, buf);
+    skin_slab_store<C>(dL_dlogits, row0, cnt, buf);
 }
 
 // ---- launchers (the C ABI has checked every argument; n > 0)

@@ -37,12 +37,12 @@
 //                             (or dW), dx and dr, each row once; every row's W and dT pass through LDS.  With dtfs
 //                             wanted, 216 threads sum W_nj dT_n over three fixed thirds of the block's rows in double; the
 //                             thirds are added in order and the block's 24 x 12 partial (double) goes to the workspace.
-//   skin_dtfs_reduce          one wave per dtfs element: lane l adds its contiguous run of block partials in block
-//                             order, then lane 0 adds the 64 runs in lane order, all in double; rows 3 are written 0.
+//   skin_dtfs_reduce          one wave per dtfs element: runs64_sum (ordered_sum.h) of its block partials, rounded to
+//                             fp32 once; rows 3 are written 0.
 // Logit rows (100 or 96 bytes) and the outputs of odd width are moved between global memory and LDS as the block's
 // contiguous slab, with 16-byte accesses: a block's slab starts at row 256 b, so a 16-byte aligned base keeps every slab
 // 16-byte aligned.  No atomics, no memsets: every gradient is bitwise reproducible, and the calls are capture-safe.
-// The activations, their reverses and the slab moves are in skin_act.h, which skinloss.hip shares.
+// The activations and their reverses are in skin_act.h, which skinloss.hip shares; the slab moves are slab.h's.
 #include "common.h"
 #include "boundary.h"
 #include "gs_math.h"
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_weights_fwd_kernel(int N, c
     __shared__ float4 buf4[SKIN_THREADS * C / 4];
     float* buf = reinterpret_cast<float*>(buf4);
     const int row0 = blockIdx.x * SKIN_THREADS, n = min(SKIN_THREADS, N - row0), t = threadIdx.x;
-    slab_load<C>(logits, row0, n, buf);
+    skin_slab_load<C>(logits, row0, n, buf);
     __syncthreads();
     if (t >= n) return;
     float x[C], W[24];
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_weights_bwd_kernel(int N, c
     __shared__ float4 buf4[SKIN_THREADS * C / 4];
     float* buf = reinterpret_cast<float*>(buf4);
     const int row0 = blockIdx.x * SKIN_THREADS, n = min(SKIN_THREADS, N - row0), t = threadIdx.x;
-    slab_load<C>(logits, row0, n, buf);
+    skin_slab_load<C>(logits, row0, n, buf);
     __syncthreads();
     float dx[C];
     if (t < n) {
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_weights_bwd_kernel(int N, c
         for (int k = 0; k < C; k++) buf[t * C + k] = dx[k];
     }
     __syncthreads();
-    slab_store<C>(dL_dlogits, row0, n, buf);
+    skin_slab_store<C>(dL_dlogits, row0, n, buf);
 }
 
 // ---- skinning
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_fwd_kernel(int N, const flo
     const float* s_tfs = reinterpret_cast<const float*>(s_tfs4);
     const int row0 = blockIdx.x * SKIN_THREADS, n = min(SKIN_THREADS, N - row0), t = threadIdx.x;
     load_tfs(tfs, s_tfs4);
-    slab_load<C>(w, row0, n, buf);
+    skin_slab_load<C>(w, row0, n, buf);
     __syncthreads();
     float W[24];
     if (t < n) {
@@ -161,8 +161,8 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_fwd_kernel(int N, const flo
             for (int c = 0; c < 3; c++) Rb[3 * r + c] = T[4 * r] * R[0][c] + T[4 * r + 1] * R[1][c] + T[4 * r + 2] * R[2][c];
     }
     __syncthreads();
-    slab_store<3>(xyz_out, row0, n, buf);
-    slab_store<9>(rot_out, row0, n, buf + 3 * SKIN_THREADS);
+    skin_slab_store<3>(xyz_out, row0, n, buf);
+    skin_slab_store<9>(rot_out, row0, n, buf + 3 * SKIN_THREADS);
 }
 
 // LDS of the backward: the logit slab, then every row's W (stride 25: no bank conflicts) and dT (stride 12); the dlogit
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_bwd_kernel(int N, const flo
     const float* s_tfs = reinterpret_cast<const float*>(s_tfs4);
     const int row0 = blockIdx.x * SKIN_THREADS, n = min(SKIN_THREADS, N - row0), t = threadIdx.x;
     load_tfs(tfs, s_tfs4);
-    slab_load<C>(w, row0, n, buf);
+    skin_slab_load<C>(w, row0, n, buf);
     __syncthreads();
     float x[C], dx[C];
     if (t < n) row_from_lds<C>(buf, t, x);
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_bwd_kernel(int N, const flo
             for (int k = 0; k < C; k++) buf[t * C + k] = dx[k];
         }
         __syncthreads();
-        slab_store<C>(dw, row0, n, buf);
+        skin_slab_store<C>(dw, row0, n, buf);
     }
 }
 
@@ -307,17 +307,8 @@ __global__ __launch_bounds__(SKIN_THREADS) void skin_bwd_kernel(int N, const flo
 __global__ __launch_bounds__(64) void skin_dtfs_reduce_kernel(int nb, const double* __restrict__ partial, float* __restrict__ dtfs) {
     __shared__ double run[64];
     const int o = blockIdx.x, l = threadIdx.x, j = o / 12, e = o % 12;
-    const int per = (nb + 63) / 64, b0 = min(nb, l * per), b1 = min(nb, b0 + per);
-    const double* p = partial + (size_t)o * nb;
-    double a = 0.0;
-    for (int b = b0; b < b1; b++) a += p[b];
-    run[l] = a;
-    __syncthreads();
-    if (l == 0) {
-        double s = 0.0;
-        for (int k = 0; k < 64; k++) s += run[k];
-        dtfs[16 * j + e] = (float)s;
-    }
+    const double s = runs64_sum(partial + (size_t)o * nb, nb, run);
+    if (l == 0) dtfs[16 * j + e] = (float)s;
     if (e == 0 && l < 4) dtfs[16 * j + 12 + l] = 0.0f;
 }
 

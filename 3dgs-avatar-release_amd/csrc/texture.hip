@@ -40,14 +40,15 @@
 //                  16-byte stores; one thread per row reads its bases' gradients from LDS and writes dL/dxyz; the latent
 //                  columns are summed over the block's rows (S = max(1, min(16, TX_THREADS / Lt)) interleaved runs per column, each
 //                  in row order, then the runs in order) into partial[Lt][blocks].
-//   tx_final       one workgroup per latent column: the block partials in a fixed order (the scheme of nonrigid.hip's
-//                  nr_final_kernel: thread t takes blocks t, t + TX_THREADS, .. in order, the DPP ladder per wave, the
-//                  waves in order).
+//   (final)        one workgroup per latent column adds its block partials: ordered_final_kernel (ordered_sum.h), waves
+//                  in order, no scale.
 //   The partition of the rows into partials depends on N, D and Lt alone -- never on the device.  No atomics, no memsets, no
 //   host synchronisation, no host memory traffic: every gradient is bitwise reproducible and the calls are capture-safe.
 #include "common.h"
 #include "boundary.h"
 #include "gs_math.h"
+#include "ordered_sum.h"
+#include "slab.h"
 
 #define TX_THREADS 256
 #define TX_LDS_FLOATS 8192  // 32 KiB: the block's slab of inp
@@ -236,11 +237,7 @@ __global__ __launch_bounds__(TX_THREADS) void tx_input_fwd_kernel(GsTextureArgs 
         }
     }
     __syncthreads();
-    const size_t off = row0 * D;
-    const int total = n * D, n4 = total >> 2;
-    float4* o4 = reinterpret_cast<float4*>(inp + off);
-    for (int k = t; k < n4; k += TX_THREADS) o4[k] = buf4[k];
-    for (int k = 4 * n4 + t; k < total; k += TX_THREADS) inp[off + k] = buf[k];
+    slab_store<TX_THREADS>(inp + row0 * D, n * D, buf);
 }
 
 __global__ __launch_bounds__(TX_THREADS) void tx_input_bwd_kernel(GsTextureArgs a, int R, const float* __restrict__ g, TxGrads gr,
@@ -253,13 +250,7 @@ __global__ __launch_bounds__(TX_THREADS) void tx_input_bwd_kernel(GsTextureArgs 
     const int n = (int)min((size_t)R, (size_t)a.N - row0);
     int sh_col, nsh, after_col, lat_col;
     tx_columns(a, &sh_col, &nsh, &after_col, &lat_col);
-    {
-        const size_t off = row0 * D;
-        const int total = n * D, n4 = total >> 2;
-        const float4* g4 = reinterpret_cast<const float4*>(g + off);
-        for (int k = t; k < n4; k += TX_THREADS) buf4[k] = g4[k];
-        for (int k = 4 * n4 + t; k < total; k += TX_THREADS) buf[k] = g[off + k];
-    }
+    slab_load<TX_THREADS>(g + row0 * D, n * D, buf);
     __syncthreads();
     for (int b = 0, col = 0; b < a.n_before; col += a.before_w[b], b++)
         if (gr.before[b]) tx_gather(buf, D, col, gr.before[b] + row0 * a.before_w[b], n, a.before_w[b]);
@@ -311,23 +302,6 @@ __global__ __launch_bounds__(TX_THREADS) void tx_input_bwd_kernel(GsTextureArgs 
     }
 }
 
-// out[c] = partial[c][0] + ... + partial[c][nb - 1], in a fixed order, c = blockIdx.x
-__global__ __launch_bounds__(TX_THREADS) void tx_final_kernel(const float* __restrict__ partial, int nb, float* __restrict__ out) {
-    __shared__ float ws[TX_THREADS / 64];
-    const int t = threadIdx.x;
-    const float* p = partial + (size_t)blockIdx.x * nb;
-    float acc = 0.0f;
-    for (int i = t; i < nb; i += TX_THREADS) acc += p[i];
-    acc = wave_sum(acc);
-    if ((t & 63) == 0) ws[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) {
-        float s = ws[0];
-        for (int w = 1; w < TX_THREADS / 64; w++) s += ws[w];
-        out[blockIdx.x] = s;
-    }
-}
-
 // ---- launchers (the C ABI has checked every argument)
 static int launch_texture_input_forward(const GsTextureArgs* a, float* inp, hipStream_t s) {
     StageScope st("texture_input", s);
@@ -343,7 +317,8 @@ static int launch_texture_input_backward(const GsTextureArgs* a, const float* g,
     hipLaunchKernelGGL(tx_input_bwd_kernel, dim3(nb), dim3(TX_THREADS), 0, s, *a, tx_rows(a->D), g, grads, dxyz, partial);
     GS_LAUNCH_CHECK("texture_input_bwd", 0, s);
     if (dlatent) {
-        hipLaunchKernelGGL(tx_final_kernel, dim3(a->latent_dim), dim3(TX_THREADS), 0, s, partial, nb, dlatent);
+        hipLaunchKernelGGL((ordered_final_kernel<TX_THREADS, WavesInOrder, false>), dim3(a->latent_dim), dim3(TX_THREADS), 0, s,
+                           (const float*)partial, nb, 1.0f, dlatent);
         GS_LAUNCH_CHECK("texture_final", 0, s);
     }
     return GS_OK;
