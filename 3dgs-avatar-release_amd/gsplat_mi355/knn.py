@@ -33,7 +33,8 @@ def knn_points(p1, p2, K=1, return_sorted=True, return_nn=False):
     K = int(K)
     if K < 1 or K > 8:
         raise NotImplementedError("knn_points: 1 <= K <= 8")
-    same = q.data_ptr() == r.data_ptr() and q.shape == r.shape
+    # the same points: a view that only starts where the reference starts (other strides) is another point set
+    same = q.data_ptr() == r.data_ptr() and q.shape == r.shape and q.stride() == r.stride()
     qd = q.detach().contiguous()
     rd = qd if same else r.detach().contiguous()
     n1, n2 = int(qd.shape[0]), int(rd.shape[0])
