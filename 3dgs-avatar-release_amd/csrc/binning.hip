@@ -137,11 +137,8 @@ __global__ __launch_bounds__(TC_THREADS) void tile_count_kernel(const uint4* __r
                                                                  uint32_t* __restrict__ seg_start, int P, int gx,
                                                                  int gy, int band_rows, int nbands, int nseg, int ntiles,
                                                                  uint32_t* __restrict__ seg_cnt,
-                                                                 uint32_t* __restrict__ tile_tot,
-                                                                 uint32_t* __restrict__ xcc_mask) {
+                                                                 uint32_t* __restrict__ tile_tot) {
     __shared__ int grid[TC_CELLS];
-    // (the chunk-parallel forward hands its work out per XCD: which XCDs this frame's launches run on)
-    if (xcc_mask && threadIdx.x == 0) atomicOr(xcc_mask, 1u << xcc_id());
     __shared__ unsigned long long sb_scratch[16];
     __shared__ uint32_t s_seg[TB_MAX_SEG + 2];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -227,10 +224,11 @@ __device__ __forceinline__ uint32_t tile_work(const uint2* __restrict__ ranges, 
 // One workgroup of 1024 threads.  HELD = true: every thread keeps the work of its (up to 32) tiles in registers, so the
 // inputs are loaded once, all loads in flight together (ntiles <= 32 * 1024); otherwise the phases re-read them.
 // LDS: hist[1024], wmax[16], wsum[16].
-// (The ordering without the chunk work list: the code every frame but a chunk-parallel one runs.  Kept apart from
-// tile_order_body below -- with the work list's code in the same function the list-writing launch took 41.8 us instead of
-// 34.5 at config 3, where not one line of it runs.)
-template <bool HELD>
+// FWD = true: the forward's ordering inside its list-writing launch (mode 2), which also marks the long lists and reports
+// the frame's statistics (LongLists); false: the stand-alone launch (modes 0 and 1), which does neither.  One instance per
+// kernel on purpose: the list-writing kernel is then compiled exactly as it is without the other caller (with one
+// shared instance its code comes out differently, and that launch's time has followed such changes before).
+template <bool HELD, bool FWD>
 __device__ __forceinline__ void tile_order_plain(const uint2* __restrict__ ranges, const uint32_t* __restrict__ keys, int mode,
                                                 int ntiles, uint32_t* __restrict__ order, const PairCount pc,
                                                 const LongLists ll, uint32_t* hist, uint32_t* wmax, uint32_t* wsum) {
@@ -284,7 +282,7 @@ __device__ __forceinline__ void tile_order_plain(const uint2* __restrict__ range
     // busy for longer than the rest of the frame takes -- one wave walks n entries in ~60 n cycles, the whole frame is
     // ~0.08 cycles per pair on 1024 SIMDs -- and is rendered by four waves per quadrant instead (render_fwd.hip): bit 31.
     uint32_t wide_from = 0xFFFFFFFFu;
-    if (mode == 2) {
+    if (FWD) {
         const unsigned long long D = *pc.dev;
         wide_from = max(FWD4_MIN_LIST, (uint32_t)min(D / FWD4_TOTAL_DIV, 0x7FFFFFFFull));
         if (ll.stats) {
@@ -327,182 +325,6 @@ __device__ __forceinline__ void tile_order_plain(const uint2* __restrict__ range
     }
 }
 
-template <bool HELD>
-__device__ __forceinline__ void tile_order_body(const uint2* __restrict__ ranges, const uint32_t* __restrict__ keys, int mode,
-                                                int ntiles, uint32_t* __restrict__ order, const PairCount pc,
-                                                const LongLists ll, uint32_t* hist, uint32_t* wmax, uint32_t* wsum) {
-    constexpr int PER = 32;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    hist[tid] = 0;
-    uint32_t held[HELD ? PER : 1];
-    uint32_t mx = 0;
-    if (HELD) {
-#pragma unroll
-        for (int i = 0; i < PER; i++) {  // (the loads alone first: all of them in flight before the first is looked at)
-            if (i * 1024 >= ntiles) break;  // workgroup-uniform
-            const int t = i * 1024 + tid;
-            held[i] = t < ntiles ? tile_work(ranges, keys, mode, t) : 0u;
-        }
-#pragma unroll
-        for (int i = 0; i < PER; i++) {
-            if (i * 1024 >= ntiles) break;
-            mx = max(mx, held[i]);
-        }
-    } else {
-        for (int t = tid; t < ntiles; t += 1024) mx = max(mx, tile_work(ranges, keys, mode, t));
-    }
-    mx = wave_max(mx);
-    if (lane == 0) wmax[wid] = mx;
-    __syncthreads();
-    mx = 0;
-    for (int w = 0; w < 16; w++) mx = max(mx, wmax[w]);
-    const float scale = mx ? 1023.0f / (float)mx : 0.f;
-    auto bin_of = [&](uint32_t w) { return 1023u - min(1023u, (uint32_t)((float)w * scale)); };
-    if (HELD) {
-#pragma unroll
-        for (int i = 0; i < PER; i++) {
-            if (i * 1024 >= ntiles) break;
-            if (i * 1024 + tid < ntiles) atomicAdd(&hist[bin_of(held[i])], 1u);
-        }
-    } else {
-        for (int t = tid; t < ntiles; t += 1024) atomicAdd(&hist[bin_of(tile_work(ranges, keys, mode, t))], 1u);
-    }
-    __syncthreads();
-    // exclusive scan of the 1024 bins
-    const uint32_t v = hist[tid];
-    const uint32_t x = wave_scan_incl(v);
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wid; w++) woff += wsum[w];
-    hist[tid] = woff + x - v;
-    __syncthreads();
-    // Small images (mark_wide, forward only): a tile whose list is long against the frame's total keeps a quadrant wave
-    // busy for longer than the rest of the frame takes -- one wave walks n entries in ~60 n cycles, the whole frame is
-    // ~0.08 cycles per pair on 1024 SIMDs -- and is rendered by four waves per quadrant instead (render_fwd.hip): bit 31.
-    uint32_t wide_from = 0xFFFFFFFFu;
-    uint32_t ch = 0;  // (mark == 2) entries per chunk of the chunk-parallel forward; 0: no tile is cut this frame
-    uint32_t xmask = 0;
-    if (mode == 2) {
-        const unsigned long long D = *pc.dev;
-        wide_from = max(FWD4_MIN_LIST, (uint32_t)min(D / (unsigned long long)ll.total_div, 0x7FFFFFFFull));
-        if (ll.mark == 2 && D <= FWDC_SPARSE_PAIRS) wide_from = min(FWD4_MIN_LIST, ll.ch_min);  // (every tile of two chunks or more)
-        if (ll.stats || ll.mark == 2) {
-            // how many such tiles, and the longest list (GsFwdArgs.frame_stats: diagnostics; the chunk size below)
-            uint32_t nlong = 0;
-            if (HELD) {
-#pragma unroll
-                for (int i = 0; i < PER; i++) {
-                    if (i * 1024 >= ntiles) break;
-                    nlong += (i * 1024 + tid < ntiles && held[i] > wide_from) ? 1u : 0u;
-                }
-            } else {
-                for (int t = tid; t < ntiles; t += 1024) nlong += tile_work(ranges, keys, mode, t) > wide_from ? 1u : 0u;
-            }
-            nlong = wave_sum(nlong);
-            __syncthreads();  // (wsum is free again: the scan above has read it)
-            if (lane == 0) wsum[wid] = nlong;
-            __syncthreads();
-            uint32_t tot = 0;
-            for (int w = 0; w < 16; w++) tot += wsum[w];
-            if (tid == 0 && ll.stats) {
-                __hip_atomic_store(&ll.stats[0], (long long)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(&ll.stats[1], (long long)mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            xmask = (ll.mark == 2 && ll.xcc_mask) ? (*ll.xcc_mask & 0xFFu) : 0u;
-            if (xmask && tot > 0 && tot <= FWDC_MAX_UNITS / 2 && D <= (unsigned long long)pc.cap) {
-                // The chunk size: sum over the marked tiles of ceil(n / ch) <= D / ch + (their number) -- the smallest
-                // power-of-two multiple of FWDC_CH_MIN for which that bound fits the unit table.  A function of the
-                // frame's counts alone (not of the order the threads arrive in): the cut, and with it the association of
-                // every sum, is the same on every run.
-                ch = ll.ch_min;
-                while (D / ch + tot > (unsigned long long)FWDC_MAX_UNITS && ch < 0x40000000u) ch <<= 1;
-            }
-            __syncthreads();  // (wmax has been read by every thread long ago; wsum by all of them just now)
-            if (tid == 0) wmax[0] = 0u;  // units handed out
-            if (tid < 16) wsum[tid] = 0u;   // [0..7] chunks given to every XCD, [8..15] items given to it
-            __syncthreads();
-        }
-        if (!ll.mark) wide_from = 0xFFFFFFFFu;
-        if (ll.mark == 2 && ch == 0) wide_from = 0xFFFFFFFFu;
-    }
-    // the launch order; (mark == 2) only the tiles of at least two chunks keep their mark
-    auto place = [&](const int t, const uint32_t wk) {
-        const bool marked = wk > wide_from && (ch == 0u || wk > ch);
-        order[atomicAdd(&hist[bin_of(wk)], 1u)] = (uint32_t)t | (marked ? 0x80000000u : 0u);
-    };
-    if (HELD) {
-#pragma unroll
-        for (int i = 0; i < PER; i++) {
-            if (i * 1024 >= ntiles) break;
-            const int t = i * 1024 + tid;
-            if (t < ntiles) place(t, held[i]);
-        }
-    } else {
-        for (int t = tid; t < ntiles; t += 1024) place(t, tile_work(ranges, keys, mode, t));
-    }
-    if (ch) {
-        // (mark == 2) The chunk work list, in a pass of its own over the launch order just written (inside the unrolled
-        // loop above its code was there 32 times).  A marked tile takes the next ceil(n / ch) units -- consecutive, chunk
-        // c at unit u0 + c -- and 4 nch items of one XCD's list.  Two steps: every thread looks at one place of the order
-        // and, for a marked tile, takes the units and the items (two atomics) and notes {tile, first unit, first item |
-        // XCD << 28, chunks} in LDS; then every WAVE writes the units and items of one noted tile at a time, a lane each
-        // (one thread per tile wrote up to 116 items one after the other: + 14 us on this launch at the avatar frame).
-        // `hist` is the list-writing kernel's bitmap here (8448 words; the ordering is done with its first 1024).
-        __syncthreads();
-        uint32_t* __restrict__ stash = hist;       // [FWDC_MAX_TILES][4]
-        uint32_t* __restrict__ nstash = &wmax[1];
-        if (tid == 0) *nstash = 0u;
-        __syncthreads();
-        const uint32_t nx = (uint32_t)__popc(xmask);
-        for (int pos = tid; pos < ntiles; pos += 1024) {
-            const uint32_t ov = order[pos];
-            if (!(ov >> 31)) continue;
-            const int t = (int)(ov & 0x7FFFFFFFu);
-            const uint32_t nch = (tile_work(ranges, keys, mode, t) + ch - 1u) / ch;
-            const uint32_t u0 = atomicAdd(&wmax[0], nch);
-            // the tile's waves all run on ONE XCD (they hand values to each other through its L2).  Which one: the
-            // marked tiles are the first of the launch order, heaviest first, and are dealt out over the XCDs the
-            // frame's launches run on in a boustrophedon (0 1 .. 7 7 .. 1 0): every XCD gets one tile of every size
-            // class, so the chunks spread about evenly.  (A look at per-XCD load counters does not: the threads of
-            // this workgroup place their tiles in the same instant and all see the same minimum -- measured, every
-            // long tile of the avatar frame on one XCD; round-robin over the units: 384 to 872 items per XCD.)  Any
-            // choice gives the same image.  The tile's 4 nch items are appended to that XCD's list in chunk order: a
-            // wave only ever waits for items in front of its own in the list
-            const uint32_t ph = (uint32_t)pos % (2u * nx);
-            uint32_t pick = ph < nx ? ph : 2u * nx - 1u - ph, best = 0;
-            for (uint32_t x = 0; x < 8; x++) {
-                if ((xmask >> x) & 1u) {
-                    if (pick == 0u) { best = x; break; }
-                    pick--;
-                }
-            }
-            const uint32_t i0 = atomicAdd(&wsum[8 + best], 4u * nch);
-            const uint32_t k = atomicAdd(nstash, 1u);
-            stash[4 * k] = (uint32_t)t;
-            stash[4 * k + 1] = u0;
-            stash[4 * k + 2] = i0 | (best << 28);
-            stash[4 * k + 3] = nch;
-        }
-        __syncthreads();
-        const uint32_t nk = *nstash;
-        for (uint32_t k = (uint32_t)wid; k < nk; k += 16) {
-            const uint32_t t = stash[4 * k], u0 = stash[4 * k + 1], ib = stash[4 * k + 2], nch = stash[4 * k + 3];
-            uint32_t* __restrict__ items = ll.cw_items + (size_t)(ib >> 28) * (FWDC_MAX_UNITS * 4) + (ib & 0x0FFFFFFFu);
-            for (uint32_t c = (uint32_t)lane; c < nch; c += 64) ll.cw_units[u0 + c] = make_uint2(t, c | (nch << 16));
-            for (uint32_t i = (uint32_t)lane; i < 4u * nch; i += 64) items[i] = (u0 + (i >> 2)) * 4u + (i & 3u);
-        }
-    }
-    if (ll.cw_hdr) {  // (workgroup-uniform) the work list's header: units in use, entries per chunk
-        __syncthreads();
-        if (tid == 0) {
-            ll.cw_hdr[0] = (mode == 2 && ch) ? wmax[0] : 0u;
-            ll.cw_hdr[1] = ch;
-        }
-        if (tid < 8) ll.cw_hdr[4 + tid] = (mode == 2 && ch) ? wsum[8 + tid] : 0u;
-    }
-}
-
 // The ordering as a launch of its own (the backward: mode 1; an empty frame: mode 0).  Its other workgroups do a side
 // job (see FillJob).
 template <bool HELD>
@@ -521,7 +343,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint2* __restric
     __shared__ uint32_t wmax[16];
     __shared__ uint32_t wsum[16];
     if (mode < 0) return;  // (the fill only: the caller uses an order it already has)
-    tile_order_body<HELD>(ranges, keys, mode, ntiles, order, pc, ll, hist, wmax, wsum);
+    tile_order_plain<HELD, false>(ranges, keys, mode, ntiles, order, pc, ll, hist, wmax, wsum);
 }
 
 // ---- writing pass.  Workgroup (block of 64 x 4 tiles, segment).  The kernel's arithmetic is trivial; what it is built
@@ -532,8 +354,6 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint2* __restric
 #ifndef TW_STOP_AFTER
 #define TW_STOP_AFTER 99  // tools/tw_parts.hip builds the kernel with parts left out: 1 prologue, 2 + bitmap clear, 3 + filter
 #endif
-// CW: workgroup 0 also builds the chunk-parallel forward's work list (a kernel of its own: the other one stays what it was)
-template <bool CW>
 __global__ __launch_bounds__(TBK_THREADS) void tile_write_kernel(const uint4* __restrict__ ranklist,
                                                                  const uint32_t* __restrict__ seg_start, int P, int gx,
                                                                  int gy, int nbx, int nblocks, int nseg, int ntiles,
@@ -552,13 +372,10 @@ __global__ __launch_bounds__(TBK_THREADS) void tile_write_kernel(const uint4* __
     if (blockIdx.x == 0) {
         // Workgroup 0: the launch order of the render kernel's tile waves (heaviest first) from the tiles' pair counts --
         // nothing in this launch needs it, so it rides along instead of being a launch of one workgroup
-        if (CW) {
-            if (ntiles <= 32 * 1024) tile_order_body<true>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
-            else tile_order_body<false>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
-        } else if (ntiles <= 32 * 1024) {
-            tile_order_plain<true>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
+        if (ntiles <= 32 * 1024) {
+            tile_order_plain<true, true>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
         } else {
-            tile_order_plain<false>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
+            tile_order_plain<false, true>(nullptr, tile_tot, 2, ntiles, order, pc, ll, bitmap, dst, dst + 16);
         }
         return;
     }
@@ -800,19 +617,14 @@ int launch_tile_lists(const uint4* ranklist, const uint32_t* chunk_pairs, uint32
         const int nbands = (gy + band_rows - 1) / band_rows;
         StageScope sc_("tile_count", s);
         hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)(nbands * nseg)), dim3(TC_THREADS), 0, s, ranklist, chunk_pairs, seg_start, P,
-                           gx, gy, band_rows, nbands, nseg, ntiles, seg_cnt, tc.tile_tot, tc.xcc_mask);
+                           gx, gy, band_rows, nbands, nseg, ntiles, seg_cnt, tc.tile_tot);
         GS_LAUNCH_CHECK("tile_count", debug, s);
     }
     {
         StageScope sc_("tile_write", s);
-        if (ll.mark == 2)
-            hipLaunchKernelGGL(tile_write_kernel<true>, dim3((unsigned)(1 + G.nblocks * nseg)), dim3(TBK_THREADS), 0, s, ranklist,
-                               seg_start, P, gx, gy, G.nbx, G.nblocks, nseg, ntiles, seg_cnt, tc.tile_tot,
-                               reinterpret_cast<uint2*>(ranges), order, pc.cap > 0 ? point_list : nullptr, pc, ll);
-        else
-            hipLaunchKernelGGL(tile_write_kernel<false>, dim3((unsigned)(1 + G.nblocks * nseg)), dim3(TBK_THREADS), 0, s, ranklist,
-                               seg_start, P, gx, gy, G.nbx, G.nblocks, nseg, ntiles, seg_cnt, tc.tile_tot,
-                               reinterpret_cast<uint2*>(ranges), order, pc.cap > 0 ? point_list : nullptr, pc, ll);
+        hipLaunchKernelGGL(tile_write_kernel, dim3((unsigned)(1 + G.nblocks * nseg)), dim3(TBK_THREADS), 0, s, ranklist,
+                           seg_start, P, gx, gy, G.nbx, G.nblocks, nseg, ntiles, seg_cnt, tc.tile_tot,
+                           reinterpret_cast<uint2*>(ranges), order, pc.cap > 0 ? point_list : nullptr, pc, ll);
         GS_LAUNCH_CHECK("tile_write", debug, s);
     }
     return GS_OK;

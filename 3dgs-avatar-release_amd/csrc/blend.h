@@ -97,8 +97,6 @@ __device__ __forceinline__ void stage_entry_convert(const float4 r0, const float
 // entry j of the batch (staged at sp0 + 48 j) leaves sp0 + 48 j in mark_e or sp0 + 48 (j + 1) in mark_o, and the last
 // blended entry of the batch, as a 1-based index into it, is max(mark_e + 48, mark_o) - sp0 over 48: ONE decode for
 // both marks (48-byte entries: x / 48 = x * 43691 >> 21 for x < 2^15).  "No entry yet" is the pair of marks that decodes to 0.
-// (render_quadrant_1 only: in render_chunk, at 80 VGPRs, marks that start from sp0 cost two spilled registers -- it keeps
-// its two decodes from 0xFFFFFFFF.)
 __device__ __forceinline__ uint32_t mark_none_even(uint32_t sp0) { return sp0 - 48u; }
 __device__ __forceinline__ uint32_t mark_none_odd(uint32_t sp0) { return sp0; }
 __device__ __forceinline__ uint32_t marks_last_entry(uint32_t mark_e, uint32_t mark_o, uint32_t sp0) {

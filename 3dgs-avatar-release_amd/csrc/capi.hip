@@ -31,18 +31,14 @@ static const TuneSwitch k_tune[GS_TUNE_COUNT] = {
     {"depth_sort", GS_TUNE_DEPTH_SORT, 1, nullptr, nullptr},  // 1 bucket sort, 0 LSD radix
     {"nt_stores", GS_TUNE_NT_STORES, 1, nullptr, nullptr},
     {"bwd_chunks", GS_TUNE_BWD_CHUNKS, 1, nullptr, nullptr},  // flip between frames only
-    // GSPLAT_FWD4=0|1|2: the forward of the tiles marked as long on small images -- one wave per quadrant, four waves x four
-    // entries per step, or a wave per chunk of the list (render_fwd.hip: render_chunk)
-    {"fwd4", GS_TUNE_FWD4, 1, "GSPLAT_FWD4", nullptr},
+    // GSPLAT_FWD4=0|1: the forward of the tiles marked as long on small images -- one wave per quadrant, or four waves x four
+    // entries per step
+    {"fwd4", GS_TUNE_FWD4, 1, "GSPLAT_FWD4", [](int v) { return v == 0 || v == 1; }},
     {"small_tiles", GS_TUNE_SMALL_TILES, BWD_CHUNK_MAX_TILES, nullptr, nullptr},  // changes the image state's size
     {"shared_qlist", GS_TUNE_SHARED_QLIST, 1, nullptr, nullptr},
     {"ones_fast", GS_TUNE_ONES_FAST, 1, nullptr, nullptr},
     {"bwd_order", GS_TUNE_BWD_ORDER, 1, nullptr, nullptr},  // 0: the backward walks the tiles in the forward's launch order (A/B: + 12 us at config 3)
     {"fwd_marks", GS_TUNE_FWD_MARKS, 1, nullptr, nullptr},  // 0: the backward sets its row marks itself (A/B)
-    // entries per chunk of the chunk-parallel forward (a power of two >= 64) ...
-    {"fwdc_ch", GS_TUNE_FWDC_CH, (int)FWDC_CH_MIN, "GSPLAT_FWDC_CH", [](int v) { return v >= 64 && (v & (v - 1)) == 0; }},
-    // ... of the tiles whose list is longer than (frame's pairs) / this (and than FWD4_MIN_LIST)
-    {"fwdc_div", GS_TUNE_FWDC_DIV, (int)FWD4_TOTAL_DIV, "GSPLAT_FWDC_DIV", [](int v) { return v >= 1; }},
 };
 struct TuneState {
     std::atomic<int> v[GS_TUNE_COUNT];
@@ -224,19 +220,6 @@ static QuadLists quad_lists(const ImgViewT<RO>& im, const BinView& b, int long_l
     ql.ck_start = ql.chunks > 1 ? writable(im.ck_start) : nullptr;
     return ql;
 }
-// ... and those of the chunk-parallel forward (render_fwd.hip: render_chunk): the work list of `list` -- this image
-// state's own, or for a second render the first render's -- and the hand-off words and records of `own`
-template <bool RO>
-static void quad_lists_chunked(QuadLists& ql, const ImgView& own, const ImgViewT<RO>& list) {
-    ql.chunked = 1;
-    ql.cw_hdr = list.cw_hdr;
-    ql.cw_units = list.cw_units;
-    ql.cw_items = list.cw_items;
-    ql.cw_q = own.cw_q;
-    ql.cw_flag = own.cw_flag;
-    ql.cw_done = own.cw_done;
-    ql.cw_rec = own.cw_rec;
-}
 static int sync_if_debug(const GsFwdArgs* a, const char* stage, hipStream_t s) {
     if (!a->debug) return GS_OK;
     const hipError_t e = hipStreamSynchronize(s);
@@ -366,15 +349,11 @@ static int forward_phase2(const GsFwdArgs* a, void* geom, size_t geom_bytes, voi
     if (rc != GS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const PairCount pc{g.count + COUNT_PAIRS, (uint32_t)cap};
-    // the marked tiles chunk-parallel (render_fwd.hip: render_chunk): the image state has the cw_* fields exactly then
-    const bool chunked = forward_chunked(im.ntiles, a->long_lists);
     if (a->P > 0) {
         rc = launch_tile_lists(g.ranklist, g.chunk_pairs, g.seg_start, a->P, im.gx, im.gy,
-                               TileCounts{im.seg_cnt, im.tile_tot, im.tile_zero_bytes, im.cw_xcc_mask}, im.ranges, im.order,
+                               TileCounts{im.seg_cnt, im.tile_tot, im.tile_zero_bytes}, im.ranges, im.order,
                                b.point_list, pc,
-                               LongLists{chunked ? 2 : (forward_small_image(im.ntiles, a->long_lists) ? 1 : 0), (long long*)a->frame_stats,
-                                         im.cw_hdr, im.cw_units, (uint32_t)gs_tune_get(GS_TUNE_FWDC_CH), im.cw_items, im.cw_xcc_mask,
-                                         chunked ? (uint32_t)gs_tune_get(GS_TUNE_FWDC_DIV) : (uint32_t)FWD4_TOTAL_DIV},
+                               LongLists{forward_small_image(im.ntiles, a->long_lists) ? 1 : 0, (long long*)a->frame_stats},
                                totals_zeroed, a->debug, s);
         if (rc != GS_OK) return rc;
     } else {
@@ -382,11 +361,10 @@ static int forward_phase2(const GsFwdArgs* a, void* geom, size_t geom_bytes, voi
         if (rc != GS_OK) return rc;
         StageScope sc_("ranges_order", s);
         rc = launch_tile_order(im.ranges, nullptr, 0, im.ntiles, im.order, pc, FillJob{nullptr, 0},
-                               LongLists{0, nullptr, im.cw_hdr, nullptr}, a->debug, s);
+                               LongLists{0, nullptr}, a->debug, s);
         if (rc != GS_OK) return rc;
     }
     QuadLists ql = quad_lists(im, b, a->long_lists);
-    if (chunked) quad_lists_chunked(ql, im, im);
     if (cap > 0) {  // the backward's row marks, set on the side by the render launch (BinLayout::marks) -- or declared unset
         // (not for a frame no backward can follow -- GsFwdArgs.forward_only: a frame rendered under no_grad)
         ql.marks = (gs_tune_get(GS_TUNE_FWD_MARKS) && !a->forward_only) ? b.marks : nullptr;
@@ -477,7 +455,6 @@ int gs_forward_shared(const GsFwdArgs* a, const void* geom_src, const void* img_
     const GeomViewRO first_g = geom_state(geom_src, a->P);
     const ImgViewRO first_im = img_state(img_src, a->W, a->H, a->long_lists);
     hipStream_t s = (hipStream_t)stream;
-    const bool chunked = forward_chunked(im.ntiles, a->long_lists);  // (im and first_im have the cw_* fields exactly then)
     QuadLists ql = quad_lists(im, b, a->long_lists);  // (qlist: read, not rewritten -- the recorded quadrant lists are what is walked)
     unsigned long long* not_ones = nullptr;
     if (a->P > 0) {
@@ -492,7 +469,7 @@ int gs_forward_shared(const GsFwdArgs* a, const void* geom_src, const void* img_
                             im.gx, im.ntiles, ql.chunks};
         rc = launch_recolor(*a, first_g.rec, first_g.tiles, g.rec, g.tiles, g.clamped, not_ones,
                             CopyJob{first_im.ranges, im.ranges, im.ntiles * 2}, CopyJob{first_im.order, im.order, im.ntiles},
-                            ZeroJob{im.cw_flag, im.cw_clear_words}, not_ones ? &so : nullptr, s);
+                            not_ones ? &so : nullptr, s);
         if (rc != GS_OK) return rc;
     } else {
         // (no Gaussians: no recolouring launch to ride in) the new image state's own copy of the tile ranges and launch order
@@ -504,16 +481,6 @@ int gs_forward_shared(const GsFwdArgs* a, const void* geom_src, const void* img_
         ql.src_qcount = first_im.qcount;        // (the fields before the checkpoints sit at the same offsets
         ql.src_n_contrib = first_im.n_contrib;  //  whatever long_lists the first render was given)
         ql.not_ones = not_ones;
-    }
-    if (chunked && a->P > 0) {
-        // the first render's work list (the copied launch order carries its marks); this state's own hand-off words
-        // (cleared by the recolouring launch) and records; walking the recorded lists also the first render's records
-        quad_lists_chunked(ql, im, first_im);
-        if (ql.src_qcount) {
-            ql.src_cw_flag = first_im.cw_flag;
-            ql.src_cw_rec = first_im.cw_rec;
-            ql.src_final_T = first_im.final_T;
-        }
     }
     ql.all_ones = im.all_ones;  // (set by the render launch: 1 iff it left the speculative image alone)
     { StageScope sc_("render_fwd", s);
@@ -669,8 +636,7 @@ int gs_binning_field(void* binning, int64_t D, int32_t W, int32_t H, int32_t fie
 }
 int gs_image_field(void* img, int32_t W, int32_t H, int32_t field, void** out) {
     if (!img || !out) return GS_E_BAD_ARG;
-    // (long_lists 0 whatever the render was given: these fields sit in front of everything that depends on it, and the
-    // chunk-parallel forward's exist without it on small images only -- null in the view otherwise)
+    // (long_lists 0 whatever the render was given: these fields sit in front of everything that depends on it)
     const ImgView im = img_state(img, W, H, 0);
     void* p = nullptr;
     switch (field) {
@@ -680,10 +646,6 @@ int gs_image_field(void* img, int32_t W, int32_t H, int32_t field, void** out) {
         case GS_IMG_QCOUNT: p = im.qcount; break;
         case GS_IMG_NCON_C: p = im.ncon_c; break;
         case GS_IMG_ORDER: p = im.order; break;
-        case GS_IMG_CW_HDR: p = im.cw_hdr; break;      // 16 words: units in use, entries per chunk, .., [4..11] items per XCD
-        case GS_IMG_CW_UNITS: p = im.cw_units; break;  // FWDC_MAX_UNITS x {tile, chunk | chunks << 16}
-        case GS_IMG_CW_FLAG: p = im.cw_flag; break;    // 4 FWDC_MAX_UNITS words: hits + 1 | dead << 31
-        case GS_IMG_CW_REC: p = im.cw_rec; break;      // 4 FWDC_MAX_UNITS records of FWDC_SLOTS x 64 floats
     }
     if (!p) return GS_E_BAD_ARG;
     *out = p;

@@ -44,8 +44,7 @@ GS_BIN_POINT_LIST, GS_BIN_QLIST, GS_BIN_FIELDS = range(3)
 # u64 word of the block GS_GEOM_COUNT names that says "a second render's colours are not all ones" (csrc/common.h:
 # COUNT_NOT_ONES; tests/test_invdepth_host.py holds the two together)
 GS_COUNT_NOT_ONES = 2
-(GS_IMG_RANGES, GS_IMG_N_CONTRIB, GS_IMG_FINAL_T, GS_IMG_QCOUNT, GS_IMG_NCON_C, GS_IMG_ORDER, GS_IMG_CW_HDR, GS_IMG_CW_UNITS,
- GS_IMG_CW_FLAG, GS_IMG_CW_REC, GS_IMG_FIELDS) = range(11)
+(GS_IMG_RANGES, GS_IMG_N_CONTRIB, GS_IMG_FINAL_T, GS_IMG_QCOUNT, GS_IMG_NCON_C, GS_IMG_ORDER, GS_IMG_FIELDS) = range(7)
 
 
 class GsAdamTensor(ctypes.Structure):  # include/gsplat_mi355.h: GsAdamTensor
@@ -312,7 +311,7 @@ def check(rc):
         raise RuntimeError("gsplat_mi355: " + msg)
 
 
-tuning_listeners = []  # called after every change of a tuning switch ("small_tiles" and "fwd4" change the image state's size:
+tuning_listeners = []  # called after every change of a tuning switch ("small_tiles" changes the image state's size:
 #                        whoever memoises the library's size queries forgets them here)
 
 

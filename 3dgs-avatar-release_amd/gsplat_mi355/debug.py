@@ -75,15 +75,6 @@ def forward_state(settings, means3D, opacities, shs=None, colors_precomp=None, s
             # launch order of the tiles (heaviest first); bit 31: rendered by four waves per quadrant (small images)
             order=field(np.uint32, 4 * gx * gy, "gs_image_field", img, W, H, _lib.GS_IMG_ORDER),
         )
-        # the chunk-parallel forward's work list and hand-off words (gs_tuning "fwd4" = 2 on a small image; else absent)
-        probe = ctypes.c_void_p(0)
-        if L.gs_image_field(img.data_ptr(), W, H, _lib.GS_IMG_CW_HDR, ctypes.byref(probe)) == 0:  # GS_OK
-            hdr = field(np.uint32, 64, "gs_image_field", img, W, H, _lib.GS_IMG_CW_HDR)
-            nu = int(hdr[0])
-            im["chunks"] = dict(
-                hdr=hdr,
-                units=field(np.uint32, 8 * nu, "gs_image_field", img, W, H, _lib.GS_IMG_CW_UNITS).reshape(-1, 2),
-                flags=field(np.uint32, 16 * nu, "gs_image_field", img, W, H, _lib.GS_IMG_CW_FLAG))
     # the tile of every list entry: the lists are stored tile after tile, so the ranges say it (upstream keeps the tile
     # id in the high half of its sort keys)
     r = im["ranges"].astype(np.int64)

@@ -1,11 +1,19 @@
 """Shared scene builders for the test-suite (CPU side: numpy/torch only)."""
 import math
+import os
 
 import numpy as np
 import torch
 
 from gsplat_mi355.camera import Camera, focal2fov, orbit_camera
 from gsplat_mi355.scenes import synthetic_cloud
+
+
+def process_fwd4():
+    """What gs_tuning "fwd4" stood at when the library was loaded -- what a test that flips it puts back: GSPLAT_FWD4 if it
+    is 0 or 1 (the library ignores every other value), else the default, 1."""
+    v = int(os.environ.get("GSPLAT_FWD4", "1"))
+    return v if v in (0, 1) else 1
 
 
 def cloud_and_camera(n, W, H, sh_degree=3, seed=0, frame=0, dist2_fn=None, heavy_tail=0.0, scale_mul=1.0, layout="box"):

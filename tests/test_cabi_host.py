@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import abi_header
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -148,9 +149,9 @@ def test_every_constant_of_the_binding_is_the_header_s(lib, header):
         assert n in bound, n
     # the field numbers of the introspection calls are ABI: all of the header's enums are bound, at these values
     fields = [n for n in header.constants if re.match(r"GS_(GEOM|BIN|IMG)_", n)]
-    assert len(fields) == 6 + 2 + 10 + 3 and set(fields) <= set(bound)  # fields + the three counts
-    assert (lib.GS_GEOM_FIELDS, lib.GS_BIN_FIELDS, lib.GS_IMG_FIELDS) == (6, 2, 10)
-    assert (lib.GS_GEOM_COUNT, lib.GS_IMG_ORDER, lib.GS_IMG_CW_REC) == (5, 5, 9)
+    assert len(fields) == 6 + 2 + 6 + 3 and set(fields) <= set(bound)  # fields + the three counts
+    assert (lib.GS_GEOM_FIELDS, lib.GS_BIN_FIELDS, lib.GS_IMG_FIELDS) == (6, 2, 6)
+    assert (lib.GS_GEOM_COUNT, lib.GS_IMG_ORDER) == (5, 5)
     assert (lib.GS_OK, lib.GS_E_BAD_ARG, lib.GS_E_EXCLUSIVE, lib.GS_E_TOO_LARGE, lib.GS_E_HIP) == (0, -1, -2, -3, -4)
 
 
@@ -224,6 +225,24 @@ def test_image_state_size_follows_the_long_lists_flag(lib):
             assert flagged == plain >= tiles * 4 * 7 * 64 * 16
         else:
             assert flagged >= plain + tiles * 4 * 7 * 64 * 16
+
+
+def test_image_state_size_does_not_depend_on_the_forward_switch(lib):
+    """The image state's layout is a function of (W, H, long_lists, "small_tiles") alone: whichever forward "fwd4" selects,
+    gs_image_bytes_for returns what the library returned at its default switches before the chunk-parallel forward (whose
+    state was part of the image state while it was switched on) left."""
+    L = lib.load()
+    a = lib.GsFwdArgs()
+    want = {(64, 64, 0): 1041920, (512, 512, 0): 66633984, (1024, 1024, 0): 13369600, (1024, 1024, 1): 266010880,
+            (17, 33, 0): 380160}
+    try:
+        for fwd4 in (0, 1):
+            lib.tuning("fwd4", fwd4)
+            for (W, H, long_lists), nbytes in want.items():
+                a.W, a.H, a.long_lists = W, H, long_lists
+                assert lib.nbytes(L.gs_image_bytes_for, ctypes.byref(a)) == nbytes, (fwd4, W, H, long_lists)
+    finally:
+        lib.tuning("fwd4", helpers.process_fwd4())
 
 
 def test_argument_validation_without_a_device(lib):
@@ -535,19 +554,19 @@ def _field_offsets(L, fn, n_fields, *shape):
 
 def test_tuning_switch_names_and_value_rules(lib):
     L = lib.load()
-    fwd4 = int(os.environ.get("GSPLAT_FWD4", "1"))  # (the process's own setting)
-    defaults = dict(xcd_map=1, depth_sort=1, nt_stores=1, bwd_chunks=1, fwd4=fwd4, small_tiles=2048, shared_qlist=1, ones_fast=1,
-                    bwd_order=1, fwd_marks=1, fwdc_ch=256, fwdc_div=320)
+    defaults = dict(xcd_map=1, depth_sort=1, nt_stores=1, bwd_chunks=1, fwd4=helpers.process_fwd4(), small_tiles=2048,
+                    shared_qlist=1, ones_fast=1, bwd_order=1, fwd_marks=1)
     try:
         for name, v in defaults.items():
             assert L.gs_tuning(name.encode(), v) == 0, name
         assert L.gs_tuning(b"no_such_switch", 1) == BAD_ARG
         assert L.gs_tuning(None, 1) == BAD_ARG
-        assert L.gs_tuning(b"fwdc_ch", 100) == BAD_ARG   # not a power of two
-        assert L.gs_tuning(b"fwdc_ch", 32) == BAD_ARG    # below 64
-        assert L.gs_tuning(b"fwdc_div", 0) == BAD_ARG
-        assert L.gs_tuning(b"fwdc_ch", 128) == 0
-        assert L.gs_tuning(b"fwdc_div", 1) == 0
+        assert L.gs_tuning(b"fwd4", 2) == BAD_ARG        # (the chunk-parallel forward, retired)
+        assert L.gs_tuning(b"fwd4", -1) == BAD_ARG
+        assert L.gs_tuning(b"fwdc_ch", 256) == BAD_ARG   # (its switches: unknown names now)
+        assert L.gs_tuning(b"fwdc_div", 320) == BAD_ARG
+        assert L.gs_tuning(b"fwd4", 0) == 0
+        assert L.gs_tuning(b"fwd4", 1) == 0
     finally:
         for name, v in defaults.items():
             lib.tuning(name, v)
@@ -556,8 +575,7 @@ def test_tuning_switch_names_and_value_rules(lib):
 def test_introspection_fields_sit_where_they_did(lib):
     """Byte offset of every gs_geom_field / gs_binning_field / gs_image_field field inside its state (the state-buffer byte
     layouts are ABI: debug.py and the tools read them), and GS_E_BAD_ARG for the first number past each range (the last
-    entry of every list).  Image fields 6-9 -- the chunk-parallel forward's state -- exist only with fwd4 = 2 on an image of
-    up to 2048 tiles."""
+    entry of every list)."""
     L = lib.load()
     assert _field_offsets(L, L.gs_geom_field, 7, 10) == [512, 768, 0, 1024, 1792, 70144, BAD_ARG]
     assert _field_offsets(L, L.gs_geom_field, 7, 200000) == [9600000, 10400000, 0, 11200000, 13600000, 18707200, BAD_ARG]
@@ -566,16 +584,8 @@ def test_introspection_fields_sit_where_they_did(lib):
         assert _field_offsets(L, L.gs_binning_field, 3, 5_000_000, W, H) == [0, 20000000, BAD_ARG]
     small = [0, 256, 16640, 49408, 33024, 49664]
     large = [0, 32768, 4227072, 12615680, 8421376, 12681216]
-    fwd4 = int(os.environ.get("GSPLAT_FWD4", "1"))  # (the process's own setting)
-    try:
-        lib.tuning("fwd4", 1)
-        assert _field_offsets(L, L.gs_image_field, 11, 64, 64) == small + [BAD_ARG] * 5
-        assert _field_offsets(L, L.gs_image_field, 11, 1024, 1024) == large + [BAD_ARG] * 5
-        lib.tuning("fwd4", 2)
-        assert _field_offsets(L, L.gs_image_field, 11, 64, 64) == small + [1632256, 1632512, 54528, 2189568, BAD_ARG]
-        assert _field_offsets(L, L.gs_image_field, 11, 1024, 1024) == large + [BAD_ARG] * 5
-    finally:
-        lib.tuning("fwd4", fwd4)
+    assert _field_offsets(L, L.gs_image_field, 7, 64, 64) == small + [BAD_ARG]
+    assert _field_offsets(L, L.gs_image_field, 7, 1024, 1024) == large + [BAD_ARG]
     out = ctypes.c_void_p(0)
     assert L.gs_geom_field(None, 10, 0, ctypes.byref(out)) == BAD_ARG
     assert L.gs_geom_field(FAKE, -1, 0, ctypes.byref(out)) == BAD_ARG

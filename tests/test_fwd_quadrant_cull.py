@@ -73,8 +73,8 @@ def _forward_code_object():
 
 def test_no_forward_kernel_divides_and_the_large_image_kernel_keeps_eight_waves():
     code, meta = _forward_code_object()
-    kernels = [k for k in code if re.search(r"render_fwd(_small|_cw)?_kernel", k)]
-    assert len(kernels) == 6, kernels  # three kernels, each for a first and a second render
+    kernels = [k for k in code if re.search(r"render_fwd(_small)?_kernel", k)]
+    assert len(kernels) == 4, kernels  # two kernels, each for a first and a second render
     for k in kernels:
         assert len(code[k]) > 200, k
         bad = [i for i in code[k] if i.startswith(("v_div_scale_f32", "v_div_fixup_f32", "v_div_fmas_f32"))]

@@ -1920,7 +1920,7 @@ def test_snug_tile_rectangles_give_bitwise_the_same_outputs_as_upstream_squares(
     try:
         _snug_vs_squares(oracle, dgr, debug, bitwise=not four_wave_forward)
     finally:
-        _lib.tuning("fwd4", int(os.environ.get("GSPLAT_FWD4", "1")))  # (the process's own setting)
+        _lib.tuning("fwd4", helpers.process_fwd4())  # (the process's own setting)
 
 
 def _snug_vs_squares(oracle, dgr, debug, bitwise):
