@@ -59,7 +59,9 @@ __device__ __forceinline__ float ring_ror1(float v) {
 // / q2 are in flight.  (Until round 3 they were issued in the first set's statement and waited for in the second's, with
 // a disassembly check at build time as the only guard; same-box A/B of the one-statement form: render_bwd 1 us faster.)
 typedef float bwd_f4 __attribute__((ext_vector_type(4)));
-template <bool SECOND>
+// OFF: byte offset of the slot the reads take from, relative to `lds_addr` (the lane's entry in slot 0): an immediate of
+// the read, so the two slots cost neither a second address register nor a select at the round start.
+template <bool SECOND, int OFF>
 __device__ __forceinline__ void split_accumulate(float (&x)[9], float (&y)[9], unsigned long long mask, float Gd, float dx,
                                                  float dy, float tdx, float tdy, float wgt, float gx, float gy,
                                                  float gz, unsigned long long m1, uint32_t lds_addr, bwd_f4& q0, bwd_f4& q1,
@@ -105,14 +107,15 @@ __device__ __forceinline__ void split_accumulate(float (&x)[9], float (&y)[9], u
                      [y6] "+v"(y[6]), [y7] "+v"(y[7]), [y8] "+v"(y[8]), [q0] "+v"(q0), [q1] "+v"(q1), [r0] "+v"(rot0), [r1] "+v"(rot1), \
                      [sv] "=&s"(save)
 #define GS_ACC_Y_IN [m] "s"(mask), [m1] "s"(m1), [a] "v"(lds_addr), [Gd] "v"(Gd), [dx] "v"(dx), [dy] "v"(dy), [tdx] "v"(tdx), \
-                    [tdy] "v"(tdy), [w] "v"(wgt), [gx] "v"(gx), [gy] "v"(gy), [gz] "v"(gz)
+                    [tdy] "v"(tdy), [w] "v"(wgt), [gx] "v"(gx), [gy] "v"(gy), [gz] "v"(gz), [o0] "n"(OFF), [o1] "n"(OFF + 16), \
+                    [o2] "n"(OFF + 32)
     if constexpr (SECOND) {
         asm volatile(
             "s_mov_b64 %[sv], exec\n\t"
             "s_andn2_b64 exec, %[m1], %[m]\n\t"
-            "ds_read_b128 %[q0], %[a]\n\t"
-            "ds_read_b128 %[q1], %[a] offset:16\n\t"
-            "ds_read_b128 %[q2], %[a] offset:32\n\t" GS_ACC_Y
+            "ds_read_b128 %[q0], %[a] offset:%[o0]\n\t"
+            "ds_read_b128 %[q1], %[a] offset:%[o1]\n\t"
+            "ds_read_b128 %[q2], %[a] offset:%[o2]\n\t" GS_ACC_Y
             : GS_ACC_Y_OUT, [q2] "+v"(q2)
             : GS_ACC_Y_IN
             : "memory", "scc");
@@ -120,9 +123,9 @@ __device__ __forceinline__ void split_accumulate(float (&x)[9], float (&y)[9], u
         asm volatile(
             "s_mov_b64 %[sv], exec\n\t"
             "s_andn2_b64 exec, %[m1], %[m]\n\t"
-            "ds_read_b128 %[q0], %[a]\n\t"
-            "ds_read_b128 %[q1], %[a] offset:16\n\t"
-            "ds_read_b32 %[q2], %[a] offset:32\n\t" GS_ACC_Y
+            "ds_read_b128 %[q0], %[a] offset:%[o0]\n\t"
+            "ds_read_b128 %[q1], %[a] offset:%[o1]\n\t"
+            "ds_read_b32 %[q2], %[a] offset:%[o2]\n\t" GS_ACC_Y
             : GS_ACC_Y_OUT, [q2] "+v"(q2.x)
             : GS_ACC_Y_IN
             : "memory", "scc");
@@ -132,10 +135,70 @@ __device__ __forceinline__ void split_accumulate(float (&x)[9], float (&y)[9], u
 #undef GS_ACC_Y_IN
 }
 
+// The LAST step of a full round (t = 15): every ring position has switched, so all 64 lanes add into x and the other
+// set's nine instructions would run under an empty exec mask -- they are not issued.  The switch reads of this step, which
+// had no lane left in this round either, fetch what the NEXT round starts with instead: position 0 of every ring (`m0`)
+// takes its entry of the next chunk from the other slot (OFF; staged at this round's start), in the shadow of the nine
+// instructions and the two ring rotations, so a round start has no read and no wait of its own.  One statement, as above.
+template <bool SECOND, int OFF>
+__device__ __forceinline__ void last_accumulate(float (&x)[9], float Gd, float dx, float dy, float tdx, float tdy, float wgt,
+                                                float gx, float gy, float gz, unsigned long long m0, uint32_t lds_addr,
+                                                bwd_f4& q0, bwd_f4& q1, bwd_f4& q2, float& rot0, float& rot1) {
+    unsigned long long save;
+#define GS_ACC_L                                     \
+        "s_mov_b64 exec, %[sv]\n\t"                  \
+        "v_fmac_f32 %[x0], %[Gd], %[dx]\n\t"         \
+        "v_fmac_f32 %[x1], %[Gd], %[dy]\n\t"         \
+        "v_fmac_f32 %[x2], %[tdx], %[dx]\n\t"        \
+        "v_fmac_f32 %[x3], %[tdx], %[dy]\n\t"        \
+        "v_fmac_f32 %[x4], %[tdy], %[dy]\n\t"        \
+        "v_add_f32 %[x5], %[x5], %[Gd]\n\t"          \
+        "v_fmac_f32 %[x6], %[w], %[gx]\n\t"          \
+        "v_fmac_f32 %[x7], %[w], %[gy]\n\t"          \
+        "v_fmac_f32 %[x8], %[w], %[gz]\n\t"          \
+        "v_mov_b32_dpp %[r0], %[r0] row_ror:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_mov_b32_dpp %[r1], %[r1] row_ror:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define GS_ACC_L_OUT [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]), [x4] "+v"(x[4]), [x5] "+v"(x[5]), \
+                     [x6] "+v"(x[6]), [x7] "+v"(x[7]), [x8] "+v"(x[8]), [q0] "+v"(q0), [q1] "+v"(q1), [r0] "+v"(rot0), [r1] "+v"(rot1), \
+                     [sv] "=&s"(save)
+#define GS_ACC_L_IN [m0] "s"(m0), [a] "v"(lds_addr), [Gd] "v"(Gd), [dx] "v"(dx), [dy] "v"(dy), [tdx] "v"(tdx), [tdy] "v"(tdy), \
+                    [w] "v"(wgt), [gx] "v"(gx), [gy] "v"(gy), [gz] "v"(gz), [o0] "n"(OFF), [o1] "n"(OFF + 16), [o2] "n"(OFF + 32)
+    if constexpr (SECOND) {
+        asm volatile(
+            "s_mov_b64 %[sv], exec\n\t"
+            "s_mov_b64 exec, %[m0]\n\t"
+            "ds_read_b128 %[q0], %[a] offset:%[o0]\n\t"
+            "ds_read_b128 %[q1], %[a] offset:%[o1]\n\t"
+            "ds_read_b128 %[q2], %[a] offset:%[o2]\n\t" GS_ACC_L
+            "s_waitcnt lgkmcnt(0)"
+            : GS_ACC_L_OUT, [q2] "+v"(q2)
+            : GS_ACC_L_IN
+            : "memory");
+    } else {
+        asm volatile(
+            "s_mov_b64 %[sv], exec\n\t"
+            "s_mov_b64 exec, %[m0]\n\t"
+            "ds_read_b128 %[q0], %[a] offset:%[o0]\n\t"
+            "ds_read_b128 %[q1], %[a] offset:%[o1]\n\t"
+            "ds_read_b32 %[q2], %[a] offset:%[o2]\n\t" GS_ACC_L
+            "s_waitcnt lgkmcnt(0)"
+            : GS_ACC_L_OUT, [q2] "+v"(q2.x)
+            : GS_ACC_L_IN
+            : "memory");
+    }
+#undef GS_ACC_L
+#undef GS_ACC_L_OUT
+#undef GS_ACC_L_IN
+}
+
 // The per-entry values the inner loop reads, as the three 16-byte quads they are staged with in LDS:
 // q0 = (x, y, A2, B2), q1 = (C2, opacity, r, g), q2 = (b, and the entry's colour in a second image of the same geometry)
 struct EntryQ {
     bwd_f4 q0, q1, q2;
+};
+template <int V>
+struct bwd_const {  // a compile-time step index, slot offset or flag handed to a generic lambda
+    static constexpr int value = V;
 };
 #define ENT_SLOTS 2  // chunks of 16 staged entries in LDS: the one the lanes are switching to, the one after it
 
@@ -144,6 +207,8 @@ struct EntryQ {
 // or 64 lanes on): here the LDS unit does it instead.  The lanes of `m1 & ~m0` (those that switch at the NEXT step) read
 // their new entry from its staged copy straight into the working registers; no other lane is written.  Issue and wait
 // sit in one block: between two blocks the compiler would be free to copy registers whose load is still in flight.
+// (The statement of its own serves position 0 in front of a wave's FIRST round only: in every later round position 0's
+// entry was read by the last step of the round before, last_accumulate.)
 template <bool SECOND>
 __device__ __forceinline__ void switch_entry(EntryQ& e, uint32_t lds_addr, unsigned long long m0, unsigned long long m1) {
     unsigned long long save;
@@ -326,7 +391,8 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
             bwd_f4* e = ent[chunk & (ENT_SLOTS - 1)][j];
             e[0] = bwd_f4{p0.x, p0.y, (-0.5f * LOG2E_F) * p0.z, -LOG2E_F * p0.w};
             e[1] = bwd_f4{(-0.5f * LOG2E_F) * p1.x, p1.y, p1.z, p1.w};
-            e[2] = bwd_f4{p2.x, q2.x, q2.y, q2.z};
+            if constexpr (SECOND) e[2] = bwd_f4{p2.x, q2.x, q2.y, q2.z};
+            else *reinterpret_cast<float*>(e + 2) = p2.x;  // (the only word of the quad a switch reads back)
         }
     };
     // The gathers are UNCONDITIONAL, at list word min(k, m - 1), and the list word is read a round before the record it
@@ -355,8 +421,9 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     gather(p0, p1, p2);                 // chunk 1 in flight during round 0
     gather_id(2 * RING + j);            // ... and the list word of chunk 2
     __syncthreads();
-    // LDS address of this lane's entry in the two slots
-    const uint32_t ent_addr0 = (uint32_t)(uintptr_t)&ent[0][j][0], ent_addr1 = (uint32_t)(uintptr_t)&ent[1][j][0];
+    // LDS address of this lane's entry in slot 0; slot 1 lies ENT_SLOT_BYTES behind it, an immediate offset of the reads
+    const uint32_t ent_addr0 = (uint32_t)(uintptr_t)&ent[0][j][0];
+    constexpr int ENT_SLOT_BYTES = RING * 3 * (int)sizeof(bwd_f4);
 
     // Two accumulator sets, named by the PARITY of the chunk they belong to: during round R the lanes
     // that have already taken their entry of chunk R (lane <= t) add into set R & 1, the others still
@@ -368,11 +435,11 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
 #pragma unroll
     for (int c9 = 0; c9 < 9; c9++) accA[c9] = accB[c9] = 0.f;
     uint32_t rowA = 0, rowB = 0;  // gradient rows of the entries the sets belong to
-    // index into pix[c][] of the pixel at this lane: ring base + (s - j) mod 16, + 16 within a round
-    uint32_t pidx = (uint32_t)(ring * RING_STRIDE + pi);
-    float2 pc[NP2];
-#pragma unroll
-    for (int c6 = 0; c6 < NP2; c6++) pc[c6] = pix[c6][pidx];
+    // index into pix[c][] of the pixel at this lane when a round starts: ring base + (16 - j) mod 16.  Step t of a round
+    // reads the constants of step t + 1 at pbase + t + 1 (the 16 values stored twice in a row: no wrap); after 16 steps the
+    // lane is back at its first pixel, so every round starts at pbase: the base never moves.
+    const uint32_t pbase = (uint32_t)(ring * RING_STRIDE + pi);
+    float2 pc[NP2];  // the constants of the pixel at this lane (read at the round start and one step ahead)
     // state of the pixel currently at this lane: transmittance and the part of Gtot not yet composited
     // (the lane loaded the pixel it starts with)
     float T = T0, Rem = gtot0;
@@ -432,16 +499,19 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
     // An entry k lives at position k mod 16 of every ring for the steps k .. k+15; the loop runs
     // s = 0 .. m+14, so every entry has seen all its pixels when the loop ends.
     const int total = m + RING - 1;
-    auto run_round = [&](const int s0, float (&X)[9], uint32_t& rowX, float (&Y)[9]) {
-        // Round start (round R = s0 / 16).  X holds the finished sums of chunk R - 2: store them.  The lanes switch to
-        // chunk R during this round (staged one round ago): its row is the one noted then.  The chunk that was in flight
-        // (R + 1) is converted and staged for the next round; the chunk after it goes in flight.
+    constexpr unsigned long long POS0 = 0x0001000100010001ull;  // position 0 of every ring
+    // Round start (round R = s0 / 16).  X holds the finished sums of chunk R - 2: store them.  The lanes switch to chunk R
+    // during this round (staged one round ago): its row is the one noted then.  The chunk that was in flight (R + 1) is
+    // converted and staged for the next round; the chunk after it goes in flight.  (Position 0 of every ring holds its
+    // entry of chunk R already: read by the last step of round R - 1, in front of round 0 by the statement below.)
+    auto round_start = [&](const int s0, float (&X)[9], uint32_t& rowX) {
+        // the pixel constants of the round's first step: the same words every round, read here so that no register carries
+        // them across the round boundary (the round-start work below hides the read)
+#pragma unroll
+        for (int c6 = 0; c6 < NP2; c6++) pc[c6] = pix[c6][pbase];
         const uint32_t row_done = rowX;
         rowX = row_staged;
-        const uint32_t ea = (s0 & RING) ? ent_addr1 : ent_addr0;  // this round's chunk: slot R & 1
-        // position 0 of every ring takes its entry now (the other positions at the end of the step before theirs)
-        switch_entry<SECOND>(cur, ea, 0ull, 0x0001000100010001ull);
-        stage(p0, p1, p2, s0 / RING + 1, row_staged);  // (behind the read above: slot (R + 1) & 1 held chunk R - 1)
+        stage(p0, p1, p2, s0 / RING + 1, row_staged);  // (slot (R + 1) & 1 held chunk R - 1: its reads ended a round ago)
         gather(p0, p1, p2);                            // chunk R + 2
         gather_id(s0 + 3 * RING + j);
         // ... and the stores BEHIND the round's loads: the counter the loads are waited for with counts the stores too, in
@@ -451,62 +521,94 @@ __global__ __launch_bounds__(64, BWD_MIN_WAVES) void render_bwd_kernel(const flo
             fold_rings(X, f);
             write_row(row_done, f);
         }
-        if (s0 > 0) pidx -= (uint32_t)RING;
 #pragma unroll
         for (int c9 = 0; c9 < 9; c9++) X[c9] = 0.f;
-        const int tend = min(RING, total - s0);
-        unsigned long long mx = 0x0001000100010001ull;  // ring positions <= t, kept up to date step by step
-        auto step = [&](const int t) {
-            const uint32_t s = (uint32_t)(s0 + t);
-            const float3 g = make_float3(pc[0].x, pc[0].y, pc[1].x);  // dL/dpixel of the pixel at this lane
-            const float pxf = pc[1].y, pyf = pc[2].x;
-            const uint32_t lim = __float_as_uint(pc[2].y);
-            const float h0 = SECOND ? pc[3].x : 0.f, h1 = SECOND ? pc[3].y : 0.f, h2 = SECOND ? pc[NP2 - 1].x : 0.f;
-            // next step's pixel constants, fetched now
-            pidx += 1u;
-#pragma unroll
-            for (int c6 = 0; c6 < NP2; c6++) pc[c6] = pix[c6][pidx];
-            const float dx = cur.q0.x - pxf, dy = cur.q0.y - pyf;
-            // A2 dx^2 + B2 dx dy + C2 dy^2 in five operations
-            const float power2 = __builtin_fmaf(cur.q0.z * dx, dx, __builtin_fmaf(cur.q0.w, dx, cur.q1.x * dy) * dy);
-            const float G = __builtin_amdgcn_exp2f(power2);
-            const float al = fminf(0.99f, cur.q1.y * G);
-            // The pair counts iff power <= 0, the entry lies before the pixel's last contributor (s < lim; a lane that
-            // has no entry yet holds zeros, i.e. alpha = 0), and alpha >= 1/255 (which implies the forward's relaxed
-            // power2 >= thr pre-test): three compares whose lane masks meet in two scalar ANDs, then one select each
-            // for alpha and G (rejected pairs carry alpha = 0).  (Until round 2: two selects more in place of the ANDs.)
-            const bool valid = (power2 <= 0.0f) && (s < lim) && (al >= (1.0f / 255.0f));
-            const float alpha = valid ? al : 0.f;
-            const float Gv = valid ? G : 0.f;
-            const float wgt = alpha * T;
-            float cg = cur.q1.z * g.x + cur.q1.w * g.y + cur.q2.x * g.z;
-            if constexpr (SECOND) cg += cur.q2.y * h0 + cur.q2.z * h1 + cur.q2.w * h2;
-            Rem = __builtin_fmaf(-cg, wgt, Rem);
-            const float one_m = 1.f - alpha;
-            const float dL_dalpha = T * cg - Rem * __builtin_amdgcn_rcpf(one_m);
-            T *= one_m;
-            const float Gd = Gv * dL_dalpha;  // G dL/dalpha; times opacity it is G dL/dG (applied per Gaussian later)
-            const float tdx = Gd * dx, tdy = Gd * dy;
-            // sums:  0: t dx   1: t dy   2: t dx^2   3: t dx dy   4: t dy^2   5: G dL/dalpha = dL/dopacity
-            //        6..8: w g_c = dL/dcolor     (t = Gd)
-            // X += ... on the lanes <= t (they have taken their entry of this round's chunk), Y += ... on the others
-            // ... and the positions that take their entry at the next step read it meanwhile (none after the round's last step)
-            const unsigned long long mx1 = (mx << 1) | 0x0001000100010001ull;
-            // ... and the pixel moves on to the next entry = the next lane: T and Rem rotate by one lane inside their ring
-            split_accumulate<SECOND>(X, Y, mx, Gd, dx, dy, tdx, tdy, wgt, g.x, g.y, g.z, mx1, ea, cur.q0, cur.q1, cur.q2, T, Rem);
-            mx = mx1;
-        };
-        // two steps per trip: the one-step-ahead pixel constants alternate between two register sets
-        int t = 0;
-        for (; t + 1 < tend; t += 2) {
-            step(t);
-            step(t + 1);
-        }
-        if (t < tend) step(t);
     };
-    for (int s0 = 0; s0 < total; s0 += 2 * RING) {
-        run_round(s0, accA, rowA, accB);
-        if (s0 + RING < total) run_round(s0 + RING, accB, rowB, accA);
+    // One step.  `pnext`: where the NEXT step's pixel constants lie; `mx`: ring positions <= t; OFF: this round's slot;
+    // LAST: step 15 of a full round (last_accumulate).
+    auto step = [&](const uint32_t s, const uint32_t pnext, const unsigned long long mx, float (&X)[9], float (&Y)[9], auto off,
+                    auto last) {
+        constexpr int OFF = decltype(off)::value;
+        const float3 g = make_float3(pc[0].x, pc[0].y, pc[1].x);  // dL/dpixel of the pixel at this lane
+        const float pxf = pc[1].y, pyf = pc[2].x;
+        const uint32_t lim = __float_as_uint(pc[2].y);
+        const float h0 = SECOND ? pc[NP2 - 2].x : 0.f, h1 = SECOND ? pc[NP2 - 2].y : 0.f, h2 = SECOND ? pc[NP2 - 1].x : 0.f;
+        // next step's pixel constants, fetched now (the round's last step fetches none: see round_start)
+        if constexpr (!decltype(last)::value) {
+#pragma unroll
+            for (int c6 = 0; c6 < NP2; c6++) pc[c6] = pix[c6][pnext];
+        }
+        const float dx = cur.q0.x - pxf, dy = cur.q0.y - pyf;
+        // A2 dx^2 + B2 dx dy + C2 dy^2 in five operations
+        const float power2 = __builtin_fmaf(cur.q0.z * dx, dx, __builtin_fmaf(cur.q0.w, dx, cur.q1.x * dy) * dy);
+        const float G = __builtin_amdgcn_exp2f(power2);
+        const float al = fminf(0.99f, cur.q1.y * G);
+        // The pair counts iff power <= 0, the entry lies before the pixel's last contributor (s < lim; a lane that
+        // has no entry yet holds zeros, i.e. alpha = 0), and alpha >= 1/255 (which implies the forward's relaxed
+        // power2 >= thr pre-test): three compares whose lane masks meet in two scalar ANDs, then one select each
+        // for alpha and G (rejected pairs carry alpha = 0).  (Until round 2: two selects more in place of the ANDs.)
+        const bool valid = (power2 <= 0.0f) && (s < lim) && (al >= (1.0f / 255.0f));
+        const float alpha = valid ? al : 0.f;
+        const float Gv = valid ? G : 0.f;
+        const float wgt = alpha * T;
+        float cg = cur.q1.z * g.x + cur.q1.w * g.y + cur.q2.x * g.z;
+        if constexpr (SECOND) cg += cur.q2.y * h0 + cur.q2.z * h1 + cur.q2.w * h2;
+        Rem = __builtin_fmaf(-cg, wgt, Rem);
+        const float one_m = 1.f - alpha;
+        const float dL_dalpha = T * cg - Rem * __builtin_amdgcn_rcpf(one_m);
+        T *= one_m;
+        const float Gd = Gv * dL_dalpha;  // G dL/dalpha; times opacity it is G dL/dG (applied per Gaussian later)
+        const float tdx = Gd * dx, tdy = Gd * dy;
+        // sums:  0: t dx   1: t dy   2: t dx^2   3: t dx dy   4: t dy^2   5: G dL/dalpha = dL/dopacity
+        //        6..8: w g_c = dL/dcolor     (t = Gd)
+        // X += ... on the lanes <= t (they have taken their entry of this round's chunk), Y += ... on the others
+        // ... and the positions that take their entry at the next step read it meanwhile
+        // ... and the pixel moves on to the next entry = the next lane: T and Rem rotate by one lane inside their ring
+        if constexpr (decltype(last)::value)
+            last_accumulate<SECOND, ENT_SLOT_BYTES - OFF>(X, Gd, dx, dy, tdx, tdy, wgt, g.x, g.y, g.z, POS0, ent_addr0, cur.q0,
+                                                          cur.q1, cur.q2, T, Rem);
+        else
+            split_accumulate<SECOND, OFF>(X, Y, mx, Gd, dx, dy, tdx, tdy, wgt, g.x, g.y, g.z, (mx << 1) | POS0, ent_addr0,
+                                          cur.q0, cur.q1, cur.q2, T, Rem);
+    };
+    // The 16 steps of a round are STRAIGHT-LINE code: the step index is a compile-time constant, so the pixel constants are
+    // read at constant offsets from `pbase` and the lane masks are constants -- no index or mask arithmetic in a round.  The
+    // wave's last round leaves the sequence behind its last step (elsewhere a scalar compare and a branch not taken per
+    // step) and with it the round loop: nothing but the two sets and their rows is alive at such an exit, so no exit costs
+    // a register move on the path the full rounds take.  Returns whether the walk ended in this round.
+    // (A run-time loop for the partial round NEXT TO the straight-line body -- in either order, inside or behind the round
+    // loop -- made the register allocator split the sets' live ranges: 100-118 VGPRs, four waves per SIMD)
+    auto run_round = [&](const int s0, float (&X)[9], uint32_t& rowX, float (&Y)[9], auto off) {
+        round_start(s0, X, rowX);
+        const int left = total - s0;  // steps still to run: all 16 of this round, or fewer
+#define GS_STEP(t)                                                                                                         \
+    step((uint32_t)(s0 + (t)), pbase + (uint32_t)((t) + 1), ((1ull << ((t) + 1)) - 1ull) * POS0, X, Y, off,                \
+         bwd_const<(t) == RING - 1>{});                                                                                    \
+    if (left <= (t) + 1) return true
+        GS_STEP(0);
+        GS_STEP(1);
+        GS_STEP(2);
+        GS_STEP(3);
+        GS_STEP(4);
+        GS_STEP(5);
+        GS_STEP(6);
+        GS_STEP(7);
+        GS_STEP(8);
+        GS_STEP(9);
+        GS_STEP(10);
+        GS_STEP(11);
+        GS_STEP(12);
+        GS_STEP(13);
+        GS_STEP(14);
+        GS_STEP(15);
+        return false;
+#undef GS_STEP
+    };
+    // position 0 of every ring takes its entry of chunk 0 now (the other positions at the end of the step before theirs)
+    switch_entry<SECOND>(cur, ent_addr0, 0ull, POS0);
+    for (int s0 = 0;; s0 += 2 * RING) {
+        if (run_round(s0, accA, rowA, accB, bwd_const<0>{})) break;
+        if (run_round(s0 + RING, accB, rowB, accA, bwd_const<ENT_SLOT_BYTES>{})) break;
     }
     {
         // the two chunks still in the sets: the one taken during the last round and the one before it

@@ -174,7 +174,8 @@ __device__ __forceinline__ void render_quadrant_1(const FwdArgs& A, const int ti
         // compiler cannot prove uniform (vzero) makes it one v_add per entry + immediate offsets; proven
         // uniform, it is rebuilt from SGPRs with a v_mov per dword and a dozen scalar adds per entry, and
         // the CU's single scalar unit becomes the bottleneck.
-        const char* sp = reinterpret_cast<const char*>(srec) + vzero;
+        // (Held as the 32-bit LDS address itself: the loop advances it inside an asm statement, below.)
+        uint32_t sp = (uint32_t)(uintptr_t)srec + vzero;
         const uint32_t kbase = kcount - (uint32_t)cnt;  // compacted index of this batch's first entry
         // One entry against the 64 pixels.  `a`, `b`, `c` = the three staged quads of the entry.
         // `mark`: set to the loop's LDS address register where the pair is blended -- the entry's index in the batch is
@@ -198,24 +199,41 @@ __device__ __forceinline__ void render_quadrant_1(const FwdArgs& A, const int ti
             C2 += c.z * w;
             // blended <=> w > 0 <=> valid and pass (pass implies T > 0): the AND of two lane masks the loop already has,
             // one scalar instruction instead of a third compare
-            mark = (valid && pass) ? (uint32_t)(uintptr_t)sp : mark;
+            mark = (valid && pass) ? sp : mark;
         };
         // The loop is software-pipelined by hand, two entries per trip: the LDS reads of the NEXT entry are issued
         // before the current one is evaluated.  With eight waves per SIMD the LDS latency hides behind the other waves
         // anyway; a lone wave on its SIMD paid the ~100 cycles of every entry's reads in full.  (Reads one entry past the
         // batch: srec has a 65th.)
-        auto ld_a = [&](int o) { return *reinterpret_cast<const float4*>(sp + o); };
-        auto ld_b = [&](int o) { return *reinterpret_cast<const float2*>(sp + o + 16); };
+        typedef float lds_v4 __attribute__((ext_vector_type(4)));
+        typedef float lds_v2 __attribute__((ext_vector_type(2)));
+        auto ld4 = [&](int o) {
+            const lds_v4 v = *(const __attribute__((address_space(3))) lds_v4*)(sp + o);
+            return make_float4(v.x, v.y, v.z, v.w);
+        };
+        auto ld_a = [&](int o) { return ld4(o); };
+        auto ld_b = [&](int o) {
+            const lds_v2 v = *(const __attribute__((address_space(3))) lds_v2*)(sp + o + 16);
+            return make_float2(v.x, v.y);
+        };
         auto ld_c = [&](int o) {
-            const float4 c = *reinterpret_cast<const float4*>(sp + o + 32);
+            const float4 c = ld4(o + 32);
             // keep the whole 16 bytes of `c` one ds_read_b128 (4 LDS cycles): only r, g, b are used in the loop, and
             // the 12-byte ds_read_b96 the compiler would pick takes 8 -- with it the loop needs 14 LDS cycles per entry
             // and wave, 56 per four SIMDs against 52 cycles of VALU issue: the kernel was LDS-bound
             asm volatile("" ::"v"(c.w));
             return c;
         };
+        // ... and the pin of the trip's last read advances `sp` to the next pair of entries, in place: as an ordinary
+        // add the compiler issued it early, held old and new address in two registers and paid a copy per trip.  (`mark`:
+        // the select of the even entry, which takes the old address, stands in front of the add.)
+        auto ld_c_advance = [&](int o, uint32_t& mark) {
+            const float4 c = ld4(o + 32);
+            asm volatile("v_add_u32 %0, 0x60, %0" : "+v"(sp), "+v"(mark) : "v"(c.w));
+            return c;
+        };
         // even entries of a run are evaluated with sp at their own address, odd ones with sp 48 bytes past theirs
-        const uint32_t sp0 = (uint32_t)(uintptr_t)sp;
+        const uint32_t sp0 = sp;
         uint32_t mark_e = mark_none_even(sp0), mark_o = mark_none_odd(sp0);  // (blend.h: marks_last_entry)
         // entries [j0, j1) of the batch (sp stands at entry j0, and at entry j1 afterwards)
         auto run = [&](const int j0, const int j1) {
@@ -226,8 +244,7 @@ __device__ __forceinline__ void render_quadrant_1(const FwdArgs& A, const int ti
                 const float4 a1 = ld_a(48), c1 = ld_c(48);
                 const float2 b1 = ld_b(48);
                 blend(a0, b0, c0, mark_e);
-                a0 = ld_a(96); c0 = ld_c(96); b0 = ld_b(96);
-                sp += 96;
+                a0 = ld_a(96); b0 = ld_b(96); c0 = ld_c_advance(96, mark_e);
                 blend(a1, b1, c1, mark_o);
             }
             if (j < j1) {
