@@ -31,13 +31,14 @@ COMMON = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-fhip-fp32-co
 # its matrix products are MFMA instructions either way; lpips: whose bias, mean and head sums are written in one order -- its
 # products are MFMA instructions either way): no FMA contraction
 STRICT = {"preprocess.hip", "knn.hip", "densify.hip", "aiap.hip", "hashgrid.hip", "skinning.hip", "skinloss.hip", "pose.hip",
-          "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip"}
+          "nonrigid.hip", "texture.hip", "mlp.hip", "mlp_wide.hip", "lpips.hip"}
 # packed fp32 (v_pk_*) issues at half rate on gfx950 (tools/valu_rate.hip), so pairing scalars buys
 # nothing and the register shuffling the SLP vectoriser adds to form the pairs costs VALU slots
 NO_SLP = {"render_fwd.hip", "render_bwd.hip"}
 SOURCES = ["capi.hip", "preprocess.hip", "radix_sort.hip", "depth_sort.hip", "binning.hip", "render_fwd.hip", "render_bwd.hip",
            "gaussian_bwd.hip", "knn.hip", "loss.hip", "prepass.hip", "optim.hip", "densify.hip", "aiap.hip", "hashgrid.hip",
-           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "lpips.hip", "debug_stats.hip",
+           "skinning.hip", "skinloss.hip", "pose.hip", "nonrigid.hip", "texture.hip", "mlp.hip", "mlp_wide.hip", "lpips.hip",
+           "debug_stats.hip",
            "second_colors.hip"]
 
 
@@ -50,6 +51,7 @@ def hipcc():
 
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "gsplat_mi355.h"),
+                                                                 os.path.join(HERE, "..", "include", "gsplat_mi355_wmlp.h"),
                                                                  os.path.abspath(__file__)]
     return max(os.path.getmtime(d) for d in deps)
 

@@ -7,7 +7,9 @@ backward without atomics (bitwise reproducible), without host synchronisation or
 * `fused_mlp(x, weights, biases, cond=None, negative_slope=0.01)` -> (N, dout), one autograd node.
 * `mlp_supported(module)` -- whether a VanillaCondMLP's configuration is one the kernels take.
 * `mlp_forward(self, coords, cond=None)` -- VanillaCondMLP.forward ("The MLPs"); a configuration outside
-  the kernels' (positional encoding, skip connections, another width) is evaluated in plain torch.
+  these kernels' (positional encoding, skip connections, width 256) goes to the wide kernels (gsplat_mi355.wide_mlp ->
+  csrc/mlp_wide.hip) where they take it, the tensors are on the GPU and wide_mlp.DISPATCH hands its class to them, and is
+  evaluated in plain torch otherwise.
 Device fp32 tensors only: the fused path has no CPU version.
 """
 import ctypes
@@ -211,11 +213,17 @@ def _torch_forward(self, coords, cond):
 
 def mlp_forward(self, coords, cond=None):
     """VanillaCondMLP.forward (models/network_utils.py:225-249) through `fused_mlp`; the parameters stay the module's own
-    lin0, lin1, ...  A configuration `mlp_supported` turns down, and a condition whose rows may differ, are evaluated in
-    plain torch."""
+    lin0, lin1, ...  A configuration `mlp_supported` turns down goes to the wide kernels where wide_mlp.vanilla_forward
+    takes it (device tensors, one condition row, its class switched on), and is evaluated in plain torch otherwise, as is
+    a condition whose rows may differ."""
     supported = self.__dict__.get("_gsplat_mlp_supported")
     if supported is None:
         supported = self.__dict__["_gsplat_mlp_supported"] = mlp_supported(self)
+    if not supported and coords.is_cuda:
+        from . import wide_mlp
+        y = wide_mlp.vanilla_forward(self, coords, cond)
+        if y is not None:
+            return y
     uses_cond = len(_cfg(self.config, "cond_in", [])) > 0
     row = None
     if supported and uses_cond:

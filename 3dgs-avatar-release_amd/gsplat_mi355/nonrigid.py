@@ -4,7 +4,7 @@
 MLP's (N, 10 + F) output to positions, scales and rotations with the three `nr_*` regularisers behind it.  Each is one
 forward launch and one backward launch (the regularisers add one small fixed-order sum): no atomics (bitwise
 reproducible), no host synchronisation, no host-to-device copy per call, capture-safe.  The MLP between them stays a torch
-module.
+module (whose forward is gsplat_mi355.mlp.mlp_forward or gsplat_mi355.wide_mlp.hannw_mlp_forward).
 
 * `pose_encode(module, rots, Jtrs)` -> (1, 24 d): the encoder's 24 per-joint outputs, before `out_layer`.
 * `hierarchical_pose_encoder_forward(self, rots, Jtrs, skinning_weight=None)` -- HierarchicalPoseEncoder.forward.
@@ -12,6 +12,8 @@ module.
   -> (xyz', scaling', rotation', feature or None, {nr_xyz, nr_scale, nr_rot} or {}).
 * `nonrigid_forward(self, gaussians, iteration, camera, compute_loss=True)` -- HashGridwithMLP.forward and MLP.forward
   (INTEGRATION.md: "The non-rigid deformer").
+* `hannw_forward(self, gaussians, iteration, camera, compute_loss=True)` -- HannwMLP.forward, whose MLP is a HannwCondMLP
+  (gsplat_mi355.wide_mlp.hannw_mlp_forward).
 One difference from the reference: with `rot_offset: mult` it writes 1 into column 6 of the MLP's output in place; the
 fused op leaves `deltas` untouched (that column takes a zero gradient either way).
 Device fp32 tensors only: there is no CPU path.
@@ -268,4 +270,22 @@ def nonrigid_forward(self, gaussians, iteration, camera, compute_loss=True):
     deformed_gaussians._xyz, deformed_gaussians._scaling, deformed_gaussians._rotation = xyz, scaling, rotation
     if self.feature_dim > 0:
         setattr(deformed_gaussians, "non_rigid_feature", feature)
+    return deformed_gaussians, loss_reg
+
+
+def hannw_forward(self, gaussians, iteration, camera, compute_loss=True):
+    """HannwMLP.forward (models/deformer/non_rigid.py:146-201) with the fused pose encoder, `self.mlp(xyz_norm, iteration,
+    cond=pose_feat)` (a HannwCondMLP: wide_mlp.hannw_mlp_forward) and the fused delta application (no feature columns).
+    Before `cfg.mlp.embedder.kick_in_iter` the deltas are multiplied by zeros, as the reference does: the MLP's parameters
+    then take ZERO gradients, not None ones, which is what keeps Adam's step count the reference's."""
+    pose_feat = hierarchical_pose_encoder_forward(self.pose_encoder, camera.rots, camera.Jtrs)
+    xyz_norm = self.aabb.normalize(gaussians.get_xyz, sym=True)
+    deltas = self.mlp(xyz_norm, iteration, cond=pose_feat)
+    if iteration < self.cfg.mlp.embedder.kick_in_iter:
+        deltas = deltas * torch.zeros_like(deltas)
+    xyz, scaling, rotation, _, loss_reg = nonrigid_apply(
+        deltas, gaussians._xyz, gaussians._scaling, gaussians._rotation, scale_offset=self.cfg.get('scale_offset', 'logit'),
+        rot_offset=self.cfg.get('rot_offset', 'add'), compute_loss=compute_loss)
+    deformed_gaussians = gaussians.clone()
+    deformed_gaussians._xyz, deformed_gaussians._scaling, deformed_gaussians._rotation = xyz, scaling, rotation
     return deformed_gaussians, loss_reg
