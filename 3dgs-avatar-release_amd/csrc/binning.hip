@@ -154,12 +154,14 @@ __global__ __launch_bounds__(TC_THREADS) void tile_count_kernel(const uint4* __r
     const int r0 = min(P, (int)s_seg[sg] * 256), r1 = min(P, (int)s_seg[sg + 1] * 256);  // this segment's ranks
     if (blockIdx.x == 0 && tid <= nseg) seg_start[tid] = s_seg[tid];
     for (int rb = r0 + tid; rb < r1; rb += 4 * TC_THREADS) {
-        uint4 e[4];  // four loads in flight per thread
+        // four loads in flight per thread: unconditional, at an in-bounds rank, and a rank beyond the segment is given
+        // "touches no tile" afterwards (a load behind `r < r1 ?` is a branch with its own wait: four trips, not one)
+        uint4 e[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int r = rb + k * TC_THREADS;
-            e[k] = r < r1 ? ranklist[r] : make_uint4(0, 0, 0, 0);
-        }
+        for (int k = 0; k < 4; k++) e[k] = ranklist[min(rb + k * TC_THREADS, P - 1)];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (rb + k * TC_THREADS >= r1) e[k].w = 0u;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (e[k].w == 0u) continue;
@@ -238,11 +240,37 @@ __device__ __forceinline__ void tile_order_plain(const uint2* __restrict__ range
     uint32_t held[HELD ? PER : 1];
     uint32_t mx = 0;
     if (HELD) {
+        // The loads alone first: all of them in flight before the first is looked at.  That holds in the generated code only
+        // with the mode decided OUTSIDE the loop (a run-time mode inside it puts every load behind its own branch and wait:
+        // one round trip per 1024 tiles) and, for the modes that add up what they load, with the loads at an in-bounds index
+        // for every lane and the sums after the last of them.
+        if (mode == 2) {
 #pragma unroll
-        for (int i = 0; i < PER; i++) {  // (the loads alone first: all of them in flight before the first is looked at)
-            if (i * 1024 >= ntiles) break;  // workgroup-uniform
-            const int t = i * 1024 + tid;
-            held[i] = t < ntiles ? tile_work(ranges, keys, mode, t) : 0u;
+            for (int i = 0; i < PER; i++) {
+                if (i * 1024 >= ntiles) break;  // workgroup-uniform
+                const int t = i * 1024 + tid;
+                held[i] = t < ntiles ? keys[t] : 0u;
+            }
+        } else {
+            // (eight tiles per thread and trip -- up to 32 registers of loaded words: one trip up to 8192 tiles)
+            constexpr int B = 8;
+#pragma unroll
+            for (int i0 = 0; i0 < PER; i0 += B) {
+                if (i0 * 1024 >= ntiles) break;
+                if (mode) {  // (one 16-byte load: the four quadrant counts of a tile are adjacent and the array is 256-byte aligned)
+                    uint4 q[B];
+#pragma unroll
+                    for (int i = 0; i < B; i++) q[i] = reinterpret_cast<const uint4*>(keys)[min((i0 + i) * 1024 + tid, ntiles - 1)];
+#pragma unroll
+                    for (int i = 0; i < B; i++) held[i0 + i] = (i0 + i) * 1024 + tid < ntiles ? (q[i].x + q[i].y) + (q[i].z + q[i].w) : 0u;
+                } else {
+                    uint2 rg[B];
+#pragma unroll
+                    for (int i = 0; i < B; i++) rg[i] = ranges[min((i0 + i) * 1024 + tid, ntiles - 1)];
+#pragma unroll
+                    for (int i = 0; i < B; i++) held[i0 + i] = (i0 + i) * 1024 + tid < ntiles ? rg[i].y - rg[i].x : 0u;
+                }
+            }
         }
 #pragma unroll
         for (int i = 0; i < PER; i++) {
@@ -391,8 +419,13 @@ __global__ __launch_bounds__(TBK_THREADS) void tile_write_kernel(const uint4* __
     // Tile ranges (upstream identifyTileRanges) and this workgroup's first slot in every list, from the counting pass:
     // first pair of tile t = pairs of all tiles before it (tile_tot) + the pairs the earlier segments put into t (seg_cnt).
     // All threads add up the tiles before the block's first row; wave r takes row r of the block -- 64 consecutive tiles,
-    // whose prefix is one wave scan -- and the tiles from its row's start to the next row's.  All loads are independent:
-    // one trip to the L2, one barrier.
+    // whose prefix is one wave scan -- and the tiles from its row's start to the next row's.  All loads are independent and
+    // there is one barrier, but the generated code (tools/load_chains.py) makes 6 to 8 dependent trips of them at 32
+    // segments: every `cond ? p[i] : 0` is a branch holding its load and a full wait, and each run-time loop waits per turn
+    // -- one for the totals, one for the row sums, ceil(sg / 8) for the segment counts, two for the first rank-list trip
+    // below.  Issuing them all in one trip (unconditional loads at clamped indices, the segment counts spread over all
+    // sixteen waves, the first rank-list trip requested up here) gave the same bits and a SLOWER launch: 34.3 -> 42.0 us in
+    // three alternating traces of a config 3 frame; the code stays as it was.
     uint32_t my_dst = 0;
     {
         const int t_blk0 = by0 * gx + bx0;

@@ -351,14 +351,26 @@ __device__ __forceinline__ void segment_starts(const uint32_t* __restrict__ chun
     const int nchunks = (P + 255) / 256;
     const int per = (nchunks + nthreads - 1) / nthreads;  // consecutive chunks per thread
     const int c0 = tid * per;
-    // (all of a thread's loads at once: four in flight, kept when they are all it has -- P <= 1024 * the workgroup's threads)
-    auto work = [&](int c) { return chunk_pairs[c] + SEG_RANK_W; };
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    const uint32_t w_prev = (c0 > 0 && c0 < nchunks) ? work(c0 - 1) : 0u;
-    unsigned long long mine = 0;
-    for (int k0 = 0; k0 < per; k0 += 4) {
+    // All of a thread's loads at once: the word before its first chunk and four of its own in flight together, kept when
+    // they are all it has (P <= 1024 * the workgroup's threads).  The loads are unconditional, at chunk min(c, last chunk),
+    // and a word outside the thread's share counts as 0 afterwards: a load behind a condition is a branch with a wait of its own.
+    const int c_last = max(nchunks - 1, 0);
+    auto batch = [&](int k0, uint32_t* w) {
+        uint32_t raw[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) w[k] = (k0 + k < per && c0 + k0 + k < nchunks) ? work(c0 + k0 + k) : 0u;
+        for (int k = 0; k < 4; k++) raw[k] = chunk_pairs[min(c0 + k0 + k, c_last)];
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = (k0 + k < per && c0 + k0 + k < nchunks) ? raw[k] + SEG_RANK_W : 0u;
+    };
+    uint32_t w[4];
+    const uint32_t raw_prev = chunk_pairs[min(max(c0 - 1, 0), c_last)];
+    batch(0, w);
+    const uint32_t w_prev = (c0 > 0 && c0 < nchunks) ? raw_prev + SEG_RANK_W : 0u;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) mine += w[k];
+    for (int k0 = 4; k0 < per; k0 += 4) {
+        batch(k0, w);
 #pragma unroll
         for (int k = 0; k < 4; k++) mine += w[k];
     }
@@ -377,10 +389,7 @@ __device__ __forceinline__ void segment_starts(const uint32_t* __restrict__ chun
     int prev_seg = -1;                            // segment of the chunk before it
     if (c0 > 0 && c0 < nchunks) prev_seg = segment_of(before - w_prev, scale, nseg);
     for (int k0 = 0; k0 < per; k0 += 4) {
-        if (per > 4) {  // (workgroup-uniform; otherwise the four words are still there)
-#pragma unroll
-            for (int k = 0; k < 4; k++) w[k] = (k0 + k < per && c0 + k0 + k < nchunks) ? work(c0 + k0 + k) : 0u;
-        }
+        if (per > 4) batch(k0, w);  // (workgroup-uniform; otherwise the four words are still there)
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int c = c0 + k0 + k;

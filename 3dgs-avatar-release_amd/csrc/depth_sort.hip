@@ -73,16 +73,19 @@ __global__ __launch_bounds__(DS_THREADS) void ds_count_kernel(const uint32_t* __
         uint32_t a[DS_WAVE_WORDS], c[DS_WAVE_WORDS], t[DS_WAVE_WORDS];
 #pragma unroll
         for (int u = 0; u < DS_WAVE_WORDS; u++) {
-            const int w = base + u * DS_THREADS + tid;
-            a[u] = w < nwaves ? wave_kmin[w] : 0xFFFFFFFFu;
-            c[u] = w < nwaves ? wave_kmax[w] : 0u;
-            t[u] = w < w0 ? wave_tiles[w] : 0u;  // (w0 <= nwaves)
+            // (unconditional, at wave min(w, nwaves - 1); what lies beyond is replaced below.  `w < nwaves ? p[w] : x` is a
+            // branch around the load with a full wait at its end: 3 x 13 dependent trips at 200k Gaussians, not one)
+            const int w = min(base + u * DS_THREADS + tid, nwaves - 1);
+            a[u] = wave_kmin[w];
+            c[u] = wave_kmax[w];
+            t[u] = wave_tiles[w];
         }
 #pragma unroll
         for (int u = 0; u < DS_WAVE_WORDS; u++) {
-            lo = min(lo, a[u]);
-            hi = max(hi, c[u]);
-            before += t[u];
+            const int w = base + u * DS_THREADS + tid;
+            lo = min(lo, w < nwaves ? a[u] : 0xFFFFFFFFu);
+            hi = max(hi, w < nwaves ? c[u] : 0u);
+            before += w < w0 ? t[u] : 0u;  // (w0 <= nwaves)
         }
     }
     for (int c = blockIdx.x * DS_THREADS + tid; c < pn.nchunks; c += gridDim.x * DS_THREADS) pn.chunk_pairs[c] = 0u;
@@ -203,8 +206,10 @@ __global__ __launch_bounds__(DS_THREADS) void ds_scatter_kernel(const uint32_t* 
     }
 #pragma unroll
     for (int u = 0; u < NB_T; u++) {
-        const int b = u * DS_THREADS + tid;
-        first[u] = b < nbp ? loc[b] + cnt[(size_t)blockIdx.x * nbp + b] : 0u;
+        // (unconditional, at bucket min(b, nbp - 1): behind `b < nbp ?` every pair of loads is a branch with a full wait at
+        // its end -- 13 dependent trips at 200k Gaussians, not one; a word beyond nbp is never used below)
+        const int b = min(u * DS_THREADS + tid, nbp - 1);
+        first[u] = loc[b] + cnt[(size_t)blockIdx.x * nbp + b];
     }
     const int ngrp = (nbp + 63) / 64;  // <= 65
     if (tid < 64) {

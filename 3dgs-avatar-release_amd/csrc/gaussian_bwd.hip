@@ -30,19 +30,26 @@ __global__ __launch_bounds__(256) void segment_reduce_kernel(int P, const int32_
     const int rs = j >> 1, h = j & 1;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a8 = 0.f;
     const bool in = i < P;
-    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
-    if (in && radii[i] > 0) {
-        const uint32_t off = __float_as_uint(rec[(size_t)i * 3 + 2].y);
-        const uint32_t nrows = 4u * tiles[i];
-        if (j < 2) {  // (what the last step needs of the record: requested now, not behind the rows)
-            r0 = rec[(size_t)i * 3];
-            r1 = rec[(size_t)i * 3 + 1];
-        }
+    // The kernel is a chain of dependent load latencies (record -> marks -> rows) times the number of wave generations, not
+    // bandwidth.  First trip: the radius, the tile count and the record, all requested together and UNCONDITIONALLY, at
+    // Gaussian min(i, P - 1) -- a culled Gaussian's record row and tile count are allocated memory like any other's
+    // (common.h: geom_layout), whatever they hold, and what they hold is not used: a culled Gaussian walks 0 rows, so its
+    // row offset is never added to a pointer that is read, and its record reads as zeros below as it always has.  (With the
+    // radius tested first, the record waited a whole trip for it.)
+    const int ic = min(i, P - 1);
+    const int32_t radius = radii[ic];
+    const uint32_t tt = tiles[ic];
+    const uint32_t off = __float_as_uint(rec[(size_t)ic * 3 + 2].y);
+    // (what the last step needs of the record: requested now, not behind the rows)
+    const float4 q0 = rec[(size_t)ic * 3], q1 = rec[(size_t)ic * 3 + 1];
+    const bool live = in && radius > 0;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r0 = live && j < 2 ? q0 : zero4, r1 = live && j < 2 ? q1 : zero4;
+    {
+        const uint32_t nrows = live ? 4u * tt : 0u;
         const size_t row0 = (size_t)off * 4;
-        // The kernel is a chain of dependent load latencies (record -> marks -> rows) times the number of wave generations,
-        // not bandwidth: a trip covers 64 rows of the Gaussian (8 per lane: most Gaussians need one or two trips), all marks
-        // of a trip are requested together, then all its rows, and the next trip's marks are requested before this trip's
-        // rows are added up.
+        // A trip covers 64 rows of the Gaussian (8 per lane: most Gaussians need one or two trips), all marks of a trip are
+        // requested together, then all its rows, and the next trip's marks are requested before this trip's rows are added up.
         constexpr int U = 8;
         uint32_t mark[U], mark_n[U];
 #pragma unroll
@@ -88,6 +95,10 @@ __global__ __launch_bounds__(256) void segment_reduce_kernel(int P, const int32_
     // t = G dL/dalpha.  Apply what is constant per Gaussian: opacity (dL/dG = opacity dL/dalpha), the
     // conic combination giving dL/dmean2D (in the log2 domain the tile kernels work in), and the -1/2 of
     // dL/dconic.
+    // (The record's words reach the arithmetic below as values the compiler knows nothing about, as they did when they came
+    // out of a branch: this file is compiled with FMA contraction, and with the zeros of a culled Gaussian visible in the
+    // expressions the products and sums fuse differently -- the 2-D mean gradients then differ in their last bits.)
+    asm volatile("" : "+v"(r0.z), "+v"(r0.w), "+v"(r1.x), "+v"(r1.y));
     if (in && j < 2) {
         const float A2 = (-0.5f * LOG2E_F) * r0.z, B2 = -LOG2E_F * r0.w, C2 = (-0.5f * LOG2E_F) * r1.x, op = r1.y;
         const float il2 = 1.0f / LOG2E_F;
