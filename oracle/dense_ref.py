@@ -38,7 +38,7 @@ def _sh_rgb(deg, sh, dirs):
 
 def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, means2D, opacities,
            shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=0,
-           scale_modifier=1.0, antialiasing=False):
+           scale_modifier=1.0, antialiasing=False, state2d=None):
     """All tensor arguments float64.  `means2D` (N,3) is the zero 'screenspace_points' tensor of
     gaussian_renderer/__init__.py:76: its gradient is defined as dL/d(NDC position of the centre),
     which is what the reference wrapper returns for it.  Returns (color[3,H,W], radii[N], aux).
@@ -49,7 +49,12 @@ def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, 
 
     aux also carries the images the rasterizer's options add, differentiable like the colour image:
     `invdepth` (1,H,W) = sum_i w_i / depth_i over the included pairs (no background term) and `opacity`
-    (1,H,W) = (1 - T_final) + T_final bg[0]; and per Gaussian `s` (ones without the option) and `o_eff` = o s."""
+    (1,H,W) = (1 - T_final) + T_final bg[0]; and per Gaussian `s` (ones without the option) and `o_eff` = o s.
+
+    `state2d` = (xy (N,2), conic (N,3)), float64: the blend takes these as the Gaussians' pixel positions and conics in
+    place of its own (culling, radii and tile rectangles stay its own).  For comparing the compositing arithmetic alone with
+    a restatement that starts from rounded per-Gaussian values: a `conic` that requires grad receives dL/dconic, and
+    `means2D` still moves the positions, but nothing flows to the 3-D inputs through either."""
     dt = torch.float64
     N = means3D.shape[0]
     V = viewmatrix.to(dt).reshape(4, 4)
@@ -125,6 +130,9 @@ def render(W, H, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, means3D, 
         raw = _sh_rgb(sh_degree, shs, dirs) + 0.5
         rgb = torch.clamp_min(raw, 0.0)
     # screen-space position seen by the blend; means2D enters in NDC units
+    if state2d is not None:
+        px, py = state2d[0][:, 0].to(dt), state2d[0][:, 1].to(dt)
+        conA, conB, conC = state2d[1].to(dt).unbind(1)
     bx = px + means2D[:, 0] * (0.5 * W)
     by = py + means2D[:, 1] * (0.5 * H)
     # depth order, ties by index (stable sort of the reference)

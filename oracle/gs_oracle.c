@@ -537,6 +537,12 @@ int or_render_backward_ex(int P, int W, int H, int64_t D, const uint32_t* ranges
                           const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
                           int n_over, const uint64_t* over_key, const uint8_t* over_act,
                           double* dL_dmean2D, double* dL_dconic, double* dL_dopacity, double* dL_dcolor);
+int or_render_backward_cond(int P, int W, int H, int64_t D, const uint32_t* ranges, const uint32_t* point_list,
+                            const float* xy, const float* conic_opacity, const float* rgb, const float* bg,
+                            const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                            int n_over, const uint64_t* over_key, const uint8_t* over_act,
+                            double* dL_dmean2D, double* dL_dconic, double* dL_dopacity, double* dL_dcolor,
+                            int64_t* cond_n, double* cond_A, double* cond_B, double* cond_R);
 int or_render_backward(int P, int W, int H, int64_t D, const uint32_t* ranges, const uint32_t* point_list,
                        const float* xy, const float* conic_opacity, const float* rgb, const float* bg,
                        const float* final_T, const uint32_t* n_contrib, const float* dL_dpix /*3HW*/,
@@ -551,9 +557,41 @@ int or_render_backward_ex(int P, int W, int H, int64_t D, const uint32_t* ranges
                           const float* final_T, const uint32_t* n_contrib, const float* dL_dpix /*3HW*/,
                           int n_over, const uint64_t* over_key, const uint8_t* over_act,
                           double* dL_dmean2D, double* dL_dconic, double* dL_dopacity, double* dL_dcolor) {
+    return or_render_backward_cond(P, W, H, D, ranges, point_list, xy, conic_opacity, rgb, bg, final_T, n_contrib, dL_dpix, n_over,
+                                   over_key, over_act, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, NULL, NULL, NULL, NULL);
+}
+/* ... and, optionally (all three or none), the CONDITION of every per-Gaussian sum: what an fp32 evaluation of it may lose.
+ *   cond_n[P]   the number of (pixel, Gaussian) pairs that contributed to Gaussian g;
+ *   cond_A[9P]  per sum e[0..8] (mean2D x/y, conic A/B/C, opacity, colour r/g/b), the sum over those pairs of the term's
+ *               ABSOLUTE FORM: the same expression with every inner addition replaced by the sum of the absolute values of
+ *               its addends -- dG_ddelx -> |gdx co0| + |gdy co1|; dL_dalpha -> T sum_c (|col_c| + Cabs_c) |g_c| +
+ *               |T_final / (1 - alpha)| sum_c |bg_c g_c|, with Cabs_c = sum alpha T |col_c| over ALL included pairs of the
+ *               pixel (the total, not the running colour behind: a walk that obtains "behind" as total minus front rounds
+ *               in proportion to the total);
+ *   cond_B[9P]  the sum over the pairs of (Q + m) x the same absolute form: Q = (|co0| dx^2 + |co2| dy^2) / 2 + |co1 dx dy|,
+ *               the condition of the exponent (an error of k ulp in `power` is k ulp x Q relative in G), and m = the pair's
+ *               1-based position among its pixel's included pairs (T is a chain of m factors).
+ *   cond_R[9P]  (may be NULL) for a walk that forms dL/dalpha FRONT TO BACK as T (c . g) - Rem / (1 - alpha), Rem = (C . g) minus
+ *               the (c_j . g) alpha_j T_j of the pairs up to this one (csrc/render_bwd.hip): Rem is a difference of numbers
+ *               of the size of the pixel's TOTAL, Gabs = sum_c (Cabs_c + |T_final bg_c|) |g_c|, whatever T the pair has, and
+ *               carries the roundings of the m pairs in front of it.  The sum over the pairs of (m + 2) x the six geometric
+ *               sums' absolute form with dL_dalpha -> Gabs / (1 - alpha); zero for the three colour sums.
+ * Evaluated in double from the walk's own fp32 values; the nine sums themselves do not depend on whether these are asked for. */
+int or_render_backward_cond(int P, int W, int H, int64_t D, const uint32_t* ranges, const uint32_t* point_list,
+                            const float* xy, const float* conic_opacity, const float* rgb, const float* bg,
+                            const float* final_T, const uint32_t* n_contrib, const float* dL_dpix /*3HW*/,
+                            int n_over, const uint64_t* over_key, const uint8_t* over_act,
+                            double* dL_dmean2D, double* dL_dconic, double* dL_dopacity, double* dL_dcolor,
+                            int64_t* cond_n, double* cond_A, double* cond_B, double* cond_R) {
     const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
+    const int cond = cond_n && cond_A && cond_B;
     double* E = (double*)calloc((size_t)(D > 0 ? D : 1) * 9, sizeof(double));
     if (!E) return -1;
+    double* EC = NULL; /* per list entry: 9 x A, 9 x B, the pair count, 6 x R */
+    if (cond) {
+        EC = (double*)calloc((size_t)(D > 0 ? D : 1) * 25, sizeof(double));
+        if (!EC) { free(E); return -1; }
+    }
     const float ddelx_dx = 0.5f * W, ddely_dy = 0.5f * H;
 #pragma omp parallel for schedule(dynamic, 1)
     for (int tile = 0; tile < gx * gy; tile++) {
@@ -574,6 +612,30 @@ int or_render_backward_ex(int P, int W, int H, int64_t D, const uint32_t* ranges
                 float last_alpha = 0.f;
                 int olo = 0, ohi = 0;
                 if (n_over > 0) ov_slice(n_over, over_key, (uint64_t)pid, &olo, &ohi);
+                double Cabs[3] = {0, 0, 0};
+                uint32_t m_pos = 0; /* included pairs of this pixel not yet walked (back to front): the current pair's position */
+                if (cond) { /* the same walk once before: the pixel's total absolute colour and its number of included pairs */
+                    float Tw = T_final;
+                    uint32_t cw = r1 - r0;
+                    for (uint32_t jj = r1; jj > r0; jj--) {
+                        uint32_t j = jj - 1;
+                        cw--;
+                        if (cw >= last_contributor) continue;
+                        const uint8_t act = olo < ohi ? ov_act(over_key, over_act, olo, ohi, j) : 0;
+                        if (act & OV_SKIP) continue;
+                        const int keep = (act & OV_KEEP) != 0;
+                        uint32_t g = point_list[j];
+                        float dx = xy[2 * g] - pxf, dy = xy[2 * g + 1] - pyf;
+                        const float* co = conic_opacity + 4 * g;
+                        float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+                        if (!keep && power > 0.0f) continue;
+                        float alpha = fminf(0.99f, co[3] * expf(power));
+                        if (!keep && alpha < 1.0f / 255.0f) continue;
+                        Tw = Tw / (1.f - alpha);
+                        for (int c = 0; c < 3; c++) Cabs[c] += (double)alpha * (double)Tw * fabs((double)rgb[3 * g + c]);
+                        m_pos++;
+                    }
+                }
                 for (uint32_t jj = r1; jj > r0; jj--) {
                     uint32_t j = jj - 1;
                     contributor--;
@@ -590,6 +652,43 @@ int or_render_backward_ex(int P, int W, int H, int64_t D, const uint32_t* ranges
                     float alpha = fminf(0.99f, co[3] * G);
                     if (!keep && alpha < 1.0f / 255.0f) continue;
                     T = T / (1.f - alpha);
+                    if (cond) {
+                        const double Td = T, Gd = G, ad = alpha, ddx = dx, ddy = dy;
+                        const double c0 = fabs((double)co[0]), c1 = fabs((double)co[1]), c2 = fabs((double)co[2]);
+                        double da = 0.0, bgabs = 0.0;
+                        double* ec = EC + (size_t)j * 25;
+                        for (int c = 0; c < 3; c++) {
+                            const double gc = fabs((double)dLp[c]);
+                            da += (fabs((double)rgb[3 * g + c]) + Cabs[c]) * gc;
+                            bgabs += fabs((double)bg[c]) * gc;
+                        }
+                        da = Td * da + fabs((double)T_final / (1.0 - ad)) * bgabs;
+                        const double dGa = fabs((double)co[3]) * da;
+                        const double agdx = fabs(Gd * ddx), agdy = fabs(Gd * ddy);
+                        double t[9];
+                        t[0] = dGa * (agdx * c0 + agdy * c1) * (double)ddelx_dx;
+                        t[1] = dGa * (agdy * c2 + agdx * c1) * (double)ddely_dy;
+                        t[2] = 0.5 * agdx * fabs(ddx) * dGa;
+                        t[3] = 0.5 * agdx * fabs(ddy) * dGa;
+                        t[4] = 0.5 * agdy * fabs(ddy) * dGa;
+                        t[5] = Gd * da;
+                        for (int c = 0; c < 3; c++) t[6 + c] = ad * Td * fabs((double)dLp[c]);
+                        const double Qm = 0.5 * (c0 * ddx * ddx + c2 * ddy * ddy) + c1 * fabs(ddx * ddy) + (double)m_pos;
+                        for (int k = 0; k < 9; k++) { ec[k] += t[k]; ec[9 + k] += Qm * t[k]; }
+                        ec[18] += 1.0;
+                        {
+                            double Gabs = 0.0;
+                            for (int c = 0; c < 3; c++) Gabs += (Cabs[c] + fabs((double)T_final * (double)bg[c])) * fabs((double)dLp[c]);
+                            const double daR = Gabs / (1.0 - ad), dGaR = fabs((double)co[3]) * daR, wm = (double)m_pos + 2.0;
+                            ec[19] += wm * dGaR * (agdx * c0 + agdy * c1) * (double)ddelx_dx;
+                            ec[20] += wm * dGaR * (agdy * c2 + agdx * c1) * (double)ddely_dy;
+                            ec[21] += wm * 0.5 * agdx * fabs(ddx) * dGaR;
+                            ec[22] += wm * 0.5 * agdx * fabs(ddy) * dGaR;
+                            ec[23] += wm * 0.5 * agdy * fabs(ddy) * dGaR;
+                            ec[24] += wm * Gd * daR;
+                        }
+                        m_pos--;
+                    }
                     float dchannel_dcolor = alpha * T;
                     float dL_dalpha = 0.0f;
                     double* e = E + (size_t)j * 9;
@@ -631,6 +730,52 @@ int or_render_backward_ex(int P, int W, int H, int64_t D, const uint32_t* ranges
         dL_dcolor[3 * g] += e[6]; dL_dcolor[3 * g + 1] += e[7]; dL_dcolor[3 * g + 2] += e[8];
     }
     free(E);
+    if (cond) {
+        memset(cond_n, 0, sizeof(int64_t) * (size_t)P);
+        memset(cond_A, 0, sizeof(double) * 9 * (size_t)P);
+        memset(cond_B, 0, sizeof(double) * 9 * (size_t)P);
+        if (cond_R) memset(cond_R, 0, sizeof(double) * 9 * (size_t)P);
+        for (int64_t j = 0; j < D; j++) {
+            uint32_t g = point_list[j];
+            const double* ec = EC + (size_t)j * 25;
+            for (int k = 0; k < 9; k++) { cond_A[9 * (size_t)g + k] += ec[k]; cond_B[9 * (size_t)g + k] += ec[9 + k]; }
+            cond_n[g] += (int64_t)ec[18];
+            if (cond_R) for (int k = 0; k < 6; k++) cond_R[9 * (size_t)g + k] += ec[19 + k];
+        }
+        free(EC);
+    }
+    return 0;
+}
+
+/* The (pixel, Gaussian) pairs the backward above sums over, as a mask[HW * P] (small frames only): the same walk, the same
+ * decisions and overrides, nothing else. */
+int or_included_pairs(int P, int W, int H, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                      const float* conic_opacity, const uint32_t* n_contrib, int n_over, const uint64_t* over_key,
+                      const uint8_t* over_act, uint8_t* mask) {
+    const int gx = (W + BLOCK_X - 1) / BLOCK_X;
+    memset(mask, 0, (size_t)W * H * P);
+    for (int pyi = 0; pyi < H; pyi++)
+        for (int pxi = 0; pxi < W; pxi++) {
+            const int tile = (pyi / BLOCK_Y) * gx + pxi / BLOCK_X;
+            const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+            const size_t pid = (size_t)pyi * W + pxi;
+            const float pxf = (float)pxi, pyf = (float)pyi;
+            int olo = 0, ohi = 0;
+            if (n_over > 0) ov_slice(n_over, over_key, (uint64_t)pid, &olo, &ohi);
+            for (uint32_t j = r0; j < r1 && j - r0 < n_contrib[pid]; j++) {
+                const uint8_t act = olo < ohi ? ov_act(over_key, over_act, olo, ohi, j) : 0;
+                if (act & OV_SKIP) continue;
+                const int keep = (act & OV_KEEP) != 0;
+                uint32_t g = point_list[j];
+                float dx = xy[2 * g] - pxf, dy = xy[2 * g + 1] - pyf;
+                const float* co = conic_opacity + 4 * g;
+                float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+                if (!keep && power > 0.0f) continue;
+                float alpha = fminf(0.99f, co[3] * expf(power));
+                if (!keep && alpha < 1.0f / 255.0f) continue;
+                mask[pid * P + g] = 1;
+            }
+        }
     return 0;
 }
 

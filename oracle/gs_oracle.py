@@ -229,10 +229,15 @@ def explain_pixels(sc, fw, pids, dev_color, dev_final_T, dev_n_contrib, eps=EXPL
     return status[:n], Overrides(key[:m], act[:m], mg[:m])
 
 
-def backward(sc, fw, dL_dpix, overrides=None):
+def backward(sc, fw, dL_dpix, overrides=None, conditioning=False):
     """Full backward for dL/dcolor = dL_dpix[3,H,W]; returns the eight gradient tensors of the
     reference wrapper (A3) plus the per-Gaussian 2-D intermediates.  `overrides`: the table the forward `fw` was
-    rendered with (its final_T / n_contrib already carry the stop decisions)."""
+    rendered with (its final_T / n_contrib already carry the stop decisions).
+
+    `conditioning`: also return the condition of every per-Gaussian sum (or_render_backward_cond): `cond_n` [P] pairs per
+    Gaussian, `cond_A` and `cond_B` [P, 9] in the order SUMS, `cond_R` [P, 9] (what a front-to-back walk that keeps "the rest
+    of the pixel" as a running difference adds: gs_oracle.c) and `sums` [P, 9], the nine sums themselves in double.  The
+    other results do not depend on the flag."""
     P, W, H = sc.P, sc.W, sc.H
     st, bn, im = fw["geom"], fw["binning"], fw["image"]
     g = np.ascontiguousarray(np.asarray(dL_dpix, np.float32).reshape(3, H, W))
@@ -242,10 +247,18 @@ def backward(sc, fw, dL_dpix, overrides=None):
     d_col = np.zeros((P, 3), np.float64)
     pl = np.ascontiguousarray(bn["point_list"]) if bn["D"] > 0 else np.zeros(1, np.uint32)
     ov = overrides.cargs() if overrides is not None else _NO_OVERRIDES
-    rc = lib().or_render_backward_ex(c_int(P), c_int(W), c_int(H), c_int64(bn["D"]), _ptr(bn["ranges"]), _ptr(pl),
-                                     _ptr(st["xy"]), _ptr(st["conic_opacity"]), _ptr(st["rgb"]), _ptr(sc.bg),
-                                     _ptr(im["final_T"]), _ptr(im["n_contrib"]), _ptr(g), ov[0], ov[1], ov[2],
-                                     _ptr(d_mean2D), _ptr(d_conic), _ptr(d_op), _ptr(d_col))
+    if conditioning:
+        c_n, c_A, c_B, c_R = np.zeros(P, np.int64), np.zeros((P, 9), np.float64), np.zeros((P, 9), np.float64), np.zeros((P, 9), np.float64)
+        rc = lib().or_render_backward_cond(c_int(P), c_int(W), c_int(H), c_int64(bn["D"]), _ptr(bn["ranges"]), _ptr(pl),
+                                           _ptr(st["xy"]), _ptr(st["conic_opacity"]), _ptr(st["rgb"]), _ptr(sc.bg),
+                                           _ptr(im["final_T"]), _ptr(im["n_contrib"]), _ptr(g), ov[0], ov[1], ov[2],
+                                           _ptr(d_mean2D), _ptr(d_conic), _ptr(d_op), _ptr(d_col),
+                                           _ptr(c_n), _ptr(c_A), _ptr(c_B), _ptr(c_R))
+    else:
+        rc = lib().or_render_backward_ex(c_int(P), c_int(W), c_int(H), c_int64(bn["D"]), _ptr(bn["ranges"]), _ptr(pl),
+                                         _ptr(st["xy"]), _ptr(st["conic_opacity"]), _ptr(st["rgb"]), _ptr(sc.bg),
+                                         _ptr(im["final_T"]), _ptr(im["n_contrib"]), _ptr(g), ov[0], ov[1], ov[2],
+                                         _ptr(d_mean2D), _ptr(d_conic), _ptr(d_op), _ptr(d_col))
     assert rc == 0
     m2 = d_mean2D.astype(np.float32)
     cn = d_conic.astype(np.float32)
@@ -262,9 +275,67 @@ def backward(sc, fw, dL_dpix, overrides=None):
     assert rc == 0
     d_means2D = np.zeros((P, 3), np.float32)
     d_means2D[:, :2] = m2
-    return dict(means3D=d_means3D, means2D=d_means2D, sh=d_sh, colors_precomp=cl,
-                opacities=d_op.astype(np.float32).reshape(P, 1), scales=d_scale, rotations=d_rot,
-                cov3D_precomp=d_cov3D, conic=cn)
+    out = dict(means3D=d_means3D, means2D=d_means2D, sh=d_sh, colors_precomp=cl,
+               opacities=d_op.astype(np.float32).reshape(P, 1), scales=d_scale, rotations=d_rot,
+               cov3D_precomp=d_cov3D, conic=cn)
+    if conditioning:
+        out.update(cond_n=c_n, cond_A=c_A, cond_B=c_B, cond_R=c_R, sums=np.concatenate([d_mean2D, d_conic, d_op[:, None], d_col], 1))
+    return out
+
+
+def included_pairs(sc, fw, overrides=None):
+    """The (pixel, Gaussian) pairs the render backward sums over, as a bool mask [H W, P] (or_included_pairs)."""
+    st, bn, im = fw["geom"], fw["binning"], fw["image"]
+    mask = np.zeros((sc.H * sc.W, sc.P), np.uint8)
+    pl = np.ascontiguousarray(bn["point_list"]) if bn["D"] > 0 else np.zeros(1, np.uint32)
+    ov = overrides.cargs() if overrides is not None else _NO_OVERRIDES
+    rc = lib().or_included_pairs(c_int(sc.P), c_int(sc.W), c_int(sc.H), _ptr(bn["ranges"]), _ptr(pl), _ptr(st["xy"]),
+                                 _ptr(st["conic_opacity"]), _ptr(im["n_contrib"]), ov[0], ov[1], ov[2], _ptr(mask))
+    assert rc == 0
+    return mask.astype(bool)
+
+
+# the nine per-Gaussian sums of the render backward, in the order of cond_A / cond_B / sums
+SUMS = ("mean2D_x", "mean2D_y", "conic_A", "conic_B", "conic_C", "opacity", "color_r", "color_g", "color_b")
+_PROBES = (0, 1, 2, 3, 4, 6, 7, 8)  # the eight of them or_preprocess_backward reads (the opacity sum is an output as it is)
+
+
+def preprocess_jacobian(sc, fw):
+    """or_preprocess_backward acts per Gaussian and is linear in its eight 2-D inputs (mean2D 2, conic 3, colour 3): eight
+    calls with one input set to 1 for every Gaussian give every Gaussian's Jacobian from the 2-D sums to the derived
+    tensors.  Returns {name: J [P, K, 9]} for means3D (K = 3), cov3D_precomp (6) and, where the scene has them, scales (3),
+    rotations (4) and sh (3 M); the last axis is indexed like SUMS (column 5, the opacity, is zero)."""
+    P = sc.P
+    st = fw["geom"]
+    a = sc.cargs()
+    J = dict(means3D=np.zeros((P, 3, 9), np.float32), cov3D_precomp=np.zeros((P, 6, 9), np.float32))
+    if sc.shs is not None:
+        J["sh"] = np.zeros((P, sc.M * 3, 9), np.float32)
+    if sc.scales is not None:
+        J["scales"], J["rotations"] = np.zeros((P, 3, 9), np.float32), np.zeros((P, 4, 9), np.float32)
+    for col in _PROBES:
+        probe = np.zeros((P, 9), np.float32)
+        probe[:, col] = 1.0
+        m2, cn, cl = (np.ascontiguousarray(probe[:, s]) for s in (slice(0, 2), slice(2, 5), slice(6, 9)))
+        d_means3D = np.zeros((P, 3), np.float32)
+        d_cov3D = np.zeros((P, 6), np.float32)
+        d_sh = np.zeros((P, sc.M * 3), np.float32) if sc.shs is not None else None
+        d_scale = np.zeros((P, 3), np.float32) if sc.scales is not None else None
+        d_rot = np.zeros((P, 4), np.float32) if sc.scales is not None else None
+        rc = lib().or_preprocess_backward(ctypes.byref(a), _ptr(st["radii"]), _ptr(st["cov3D"]), _ptr(st["clamped"]),
+                                          _ptr(m2), _ptr(cn), _ptr(cl), _ptr(d_means3D), _ptr(d_sh),
+                                          _ptr(d_cov3D), _ptr(d_scale), _ptr(d_rot))
+        assert rc == 0
+        for name, v in (("means3D", d_means3D), ("cov3D_precomp", d_cov3D), ("sh", d_sh), ("scales", d_scale), ("rotations", d_rot)):
+            if v is not None:
+                J[name][:, :, col] = v
+    return J
+
+
+def through_jacobian(J, v):
+    """|J_i| v_i per Gaussian: J [P, K, 9], v [P, 9] -> [P, K] in double (the condition of a derived tensor's rows from
+    the conditions of the nine sums; with v = the sums themselves and without the absolute value, the rows)."""
+    return np.einsum("pkj,pj->pk", np.abs(np.asarray(J, np.float64)), np.asarray(v, np.float64))
 
 
 def mark_visible(means3D, viewmatrix):
